@@ -14,9 +14,11 @@ bounded by 32-bit base indices), 23 GB of the 288.
              sub-batch i+1 runs on its own stream beside the lookup / map kernels of sub-batch i.
   value    = read bases of all ranks x steps / max-over-ranks wall time of the K timed steps.
 
-Behind the timed region the same context runs a few steps with the second stream off: those per-kernel
-durations are of kernels running alone (what `roofline` quotes and what the rocprofv3 summaries in
-profiles/ hold); the durations measured inside the pipelined steps are reported beside them.
+A plain run sets up, warms up, times the steps and prints the line (--dump-outputs DIR: and writes the outputs of
+one more step of the same path).  --full adds the rest: behind the timed region the same context runs a few steps with the second
+stream off (per-kernel durations of kernels running alone, what `roofline.kernels_alone` quotes and what the rocprofv3
+summaries in profiles/ hold), the clock and power of the GPU during the timed steps, the CPU baseline, the end-to-end
+(file to file) leg and the other workloads.
 
 N > 1: one process per GPU (the driver launches `python -m torch.distributed.run ... bench.py --gpus N`;
 a bare `python bench.py --gpus N` starts those N ranks itself as a child process).  Reads shard, the contig
@@ -27,6 +29,7 @@ sub-batches; --weak gives every rank a whole read set of its own instead.
 Prints ONE JSON line on rank 0.
 """
 import argparse
+import contextlib
 import hashlib
 import json
 import os
@@ -53,14 +56,24 @@ def parse_args(argv=None):
                     "more and smaller ones cost more than they hide: profiles/r04_strong_share_sweep.txt)")
     ap.add_argument("--scale", type=float, default=1.0, help="shrink the workload (debugging only; reported)")
     ap.add_argument("--batch-bases", type=float, default=3.95e9, help="read bases per device batch")
-    ap.add_argument("--serial-steps", type=int, default=2, help="steps of the kernels-alone pass behind the timed region (0 = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the other single-GPU configs (other_workloads)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the kernels-alone pass, the clock / power of the GPU during the timed steps, "
+                    "the CPU baseline, the end-to-end leg and the other workloads (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, one more step of the same path whose outputs are written as DIR/<name>.npy "
+                    "(float64; a fixed, seeded sample of the reads' mappings, hits and PAF records + every sub-batch's counts; rank 0's share); "
+                    "the run fails if its counts are not those the line reports")
+    ap.add_argument("--serial-steps", type=int, default=None, help="steps of the kernels-alone pass behind the timed region (0 = none; default 2 with --full, else 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the end-to-end leg")
+    ap.add_argument("--no-others", action="store_true", help="--full without the other single-GPU configs (other_workloads)")
     ap.add_argument("--e2e-bases", type=float, default=32e9, help="read bases of the end-to-end (file to file) leg")
     ap.add_argument("--lib", default=None, help="C-ABI library to load (tests point this at the SIMT-mock build)")
     ap.add_argument("--spawn-check", action="store_true", help="ranks only report the world size (CPU test of the launcher)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.serial_steps is None:
+        args.serial_steps = 2 if args.full else 0
+    return args
 
 
 def spawn_ranks(args):
@@ -273,9 +286,10 @@ class Comm:
             self.dist.destroy_process_group()
 
 
-def run_workload(dev, comm, name, args, steps, warmup, rank, world, serial_steps):
+def run_workload(dev, comm, name, args, steps, warmup, rank, world, serial_steps, dump=False):
     """Generates workload `name` on the device, runs the contig stage once, `warmup` + `steps` timed pipelined steps and
-    `serial_steps` steps with the second stream off.  Returns the measurements; the workload stays open in R["wl"]."""
+    `serial_steps` steps with the second stream off; dump: the outputs of one more step of the same path in R["outputs"] (OutputSampler).
+    Returns the measurements; the workload stays open in R["wl"]."""
     import numpy as np
     from ntlink_amd import synth
     W = synth.workload(name, args.scale)
@@ -313,21 +327,23 @@ def run_workload(dev, comm, name, args, steps, warmup, rank, world, serial_steps
     for d in devs[1:]:
         d.prof_enable(True)
 
-    def run_batches(d, items, collect, acc):
+    def run_batches(d, items, collect, acc, sink=None):
         held = []
 
         def take(n_keep):  # counts are asked for two sub-batches late: the device never waits for the host's question
             while len(held) > n_keep:
-                rsk, res = held.pop(0)
-                acc["read_mx"] += rsk.count
-                acc["strips"] = acc.get("strips", 0) + rsk.strips
-                acc["index_hits"] += res.n_index_hits
-                acc["counts"] = [a + b for a, b in zip(acc["counts"], res.counts())]
-                res.close()
+                j, rsk, res = held.pop(0)
+                if collect:
+                    acc["read_mx"] += rsk.count
+                    acc["strips"] = acc.get("strips", 0) + rsk.strips
+                    acc["index_hits"] += res.n_index_hits
+                    acc["counts"] = [a + b for a, b in zip(acc["counts"], res.counts())]
+                if not (sink and sink(j, rsk, res)):  # a sink that returns True keeps the result open (and closes it itself)
+                    res.close()
                 rsk.close()
 
         trace = os.environ.get("NTL_BENCH_TRACE")
-        for rb, rl in items:
+        for j, (rb, rl) in items:
             t_a = time.perf_counter()
             # as pipeline.run_pair makes it: looked up in the index while emitted (no separate probe pass), and for this map only (no records)
             rsk = d.sketch(rb, k, w, index=ix, records=os.environ.get("NTL_BENCH_RECORDS", "0") == "1")
@@ -335,24 +351,26 @@ def run_workload(dev, comm, name, args, steps, warmup, rank, world, serial_steps
             res = d.map(ix, rsk, rl, **params)  # queued behind it; nothing waits
             if trace:
                 print(f"bench trace: sketch call {1e3 * (t_b - t_a):.3f} ms, map call {1e3 * (time.perf_counter() - t_b):.3f} ms", file=sys.stderr)
-            if collect:
-                held.append((rsk, res))
+            if collect or sink:
+                held.append((j, rsk, res))
                 take(2)
             else:
                 res.close()
                 rsk.close()
         take(0)
 
-    def step(collect=False):
+    def step(collect=False, sink=None):
+        """sink(sub-batch, sketch, result): every sub-batch's result, taken two sub-batches late as collect takes its counts; a sink must
+        not download there (ntl_mapres_download drains the main stream, which would serialise the sub-batches)"""
         if collect:
             stats.update(read_mx=0, index_hits=0, counts=[0, 0, 0], strips=0)
-        items = list(zip(wl.read_batches, wl.read_lens))
+        items = list(enumerate(zip(wl.read_batches, wl.read_lens)))
         if n_streams == 1:
-            run_batches(dev, items, collect, stats)
+            run_batches(dev, items, collect, stats, sink)
             return
         import threading
         accs = [dict(read_mx=0, index_hits=0, counts=[0, 0, 0]) for _ in devs]
-        ths = [threading.Thread(target=run_batches, args=(d, items[i::n_streams], collect, accs[i])) for i, d in enumerate(devs)]
+        ths = [threading.Thread(target=run_batches, args=(d, items[i::n_streams], collect, accs[i], sink)) for i, d in enumerate(devs)]
         for t in ths:
             t.start()
         for t in ths:
@@ -369,17 +387,42 @@ def run_workload(dev, comm, name, args, steps, warmup, rank, world, serial_steps
     for d in devs:
         d.prof_reset()
     comm.barrier(devs)
-    with DeviceStatePoller(int(os.environ.get("LOCAL_RANK", "0"))) as poller:
+    poller = DeviceStatePoller(int(os.environ.get("LOCAL_RANK", "0"))) if args.full else None
+    with poller or contextlib.nullcontext():
         t0 = time.perf_counter()
         for _ in range(steps):
             step()
         comm.barrier(devs)  # ntl_ctx_sync: also where a failure of queued work nobody looked at is raised
         elapsed = time.perf_counter() - t0
-    device_state = poller.summary()
+    device_state = poller.summary() if poller else None
     prof = {nm: tuple(sum(x) for x in zip(*[d.prof_get(nm) for d in devs])) for nm in STAGES}
     if stats["read_mx"] is None:
         step(collect=True)
         comm.barrier(devs)
+    # ---- what the timed steps computed: one more step of the same path after the clock stops -- the same calls queued in the same
+    # order, the window stage of sub-batch i + 1 on its own stream beside the lookup / map of sub-batch i.  Inside the step the sink only
+    # asks for counts, two sub-batches late as the collect step does (each waits on its own result's event, not on the stream), and
+    # keeps the results of up to DUMP_BATCHES sub-batches spread over the step open; they are downloaded and sampled when the step is
+    # over (a download waits for everything queued on the stream).  Its counts must be those of the collect step: a step that does
+    # not compute the same thing every time fails the run instead of dumping one of its answers.
+    outputs = None
+    if dump:
+        sampler = OutputSampler([len(rl) for rl in wl.read_lens])
+        step(sink=sampler.add)
+        dev.sync()  # rank 0 only: no collective here
+        if comm.use_cuda:
+            import torch
+            free, total = torch.cuda.mem_get_info()
+            print(f"bench: --dump-outputs holds the results of {len(sampler.open)} of {len(wl.read_lens)} sub-batches; device memory in use "
+                  f"{(total - free) / 1e9:.1f} GB of {total / 1e9:.1f}", file=sys.stderr)
+        sampler.finish()
+        outputs = sampler.arrays()
+        c = outputs["counts"].sum(axis=0)
+        seen = [int(x) for x in c[1:]]
+        want = [stats["read_mx"], stats["index_hits"], *stats["counts"]]
+        if seen != want:
+            raise RuntimeError(f"--dump-outputs: the step's read minimizers, index hits, mappings, hits and PAF records {seen} differ from "
+                               f"those of the collect step {want}: the path does not compute the same thing from step to step")
     # ---- kernels alone: the same steps with the window stage back on the one stream
     serial = None
     pipelined = dev.pipelined
@@ -415,7 +458,92 @@ def run_workload(dev, comm, name, args, steps, warmup, rank, world, serial_steps
     return dict(name=name, W=W, wl=wl, ix=ix, csk=csk, params=params, stats=stats, gen_s=gen_s, contig_stage_ms=contig_stage_ms,
                 contig_prof=contig_prof, contig_mx=contig_mx, index_size=index_size, elapsed=elapsed_max, total_bases=total_bases,
                 prof=prof, serial=serial, pipelined=pipelined, per_rank_ms=per_rank_ms, per_rank_bases=per_rank_bases, steps=steps,
-                n_streams=n_streams, ranks_seen=ranks_seen, ranks=ranks, batch_bases=batch_bases, device_state=device_state)
+                n_streams=n_streams, ranks_seen=ranks_seen, ranks=ranks, batch_bases=batch_bases, device_state=device_state,
+                outputs=outputs)
+
+
+DUMP_SEED = 20240607          # which reads --dump-outputs samples: fixed, so that two builds are compared on the same reads
+DUMP_BATCHES = 8              # sub-batches whose results are held to the end of the dump step (C3: 65 GB of device memory in use with 8 held)
+DUMP_READS = 8192             # reads sampled from those sub-batches (C3: about 8 k mappings and 130 k hits)
+DUMP_MAX_BYTES = 64 << 20
+
+
+class OutputSampler:
+    """The outputs of one step for --dump-outputs.  add(j, sketch, result) is the step's sink: it takes sub-batch j's counts and keeps
+    the result open if j is one of the DUMP_BATCHES sub-batches spread evenly over the step (the first and the last among them);
+    finish() downloads those after the step, one at a time, and samples each as it arrives (take).  arrays() -> {name: float64 array}:
+      counts  per sub-batch: reads, read minimizers, index hits, mappings, hits, PAF records (the whole step, exact);
+      maps    read, contig, hits of the mappings of DUMP_READS reads drawn with DUMP_SEED from the held sub-batches' reads (read = its
+              index in the step, sub-batches in order), in the order the device hands them out;
+      hits    read, contig, contig position, read position, contig strand, read strand of those mappings' hits, mapping by mapping
+              (maps[].hit_off / n_hits into the sub-batch's hit array);
+      pafs    read, contig, q_start, q_end, t_start, t_end, hits, strand of their PAF records.
+    Every field is a u32 or smaller: float64 holds it exactly.  At most DUMP_MAX_BYTES in all (hits cut at the end beyond that)."""
+
+    def __init__(self, reads_per_batch):
+        import numpy as np
+        n = np.asarray(reads_per_batch, np.int64)
+        self.n, self.base = n, np.concatenate(([0], np.cumsum(n)[:-1]))
+        self.held = sorted(set(np.linspace(0, len(n) - 1, min(len(n), DUMP_BATCHES)).round().astype(int).tolist()))
+        pool = np.concatenate([np.arange(self.base[j], self.base[j] + n[j]) for j in self.held])
+        self.pick = np.sort(np.random.default_rng(DUMP_SEED).choice(pool, size=min(len(pool), DUMP_READS), replace=False))
+        self.counts = [None] * len(n)
+        self.parts = {}
+        self.open = {}
+
+    def add(self, j, rsk, res):
+        self.count(j, rsk.count, res.n_index_hits, res.counts())
+        if j in self.held:
+            self.open[j] = res
+            return True
+        return False
+
+    def count(self, j, n_mx, n_ix, counts):
+        self.counts[j] = [int(self.n[j]), n_mx, n_ix, *counts]
+
+    def finish(self):
+        for j in sorted(self.open):
+            res = self.open.pop(j)
+            try:
+                self.take(j, res.download())
+            finally:
+                res.close()
+
+    def take(self, j, r):
+        import numpy as np
+        m, h, p = r["maps"], r["hits"], r["pafs"]
+        n, base = int(self.n[j]), int(self.base[j])
+        mine = self.pick[(self.pick >= base) & (self.pick < base + n)] - base
+        sm = m[np.isin(m["read"], mine)]
+        sp = p[np.isin(p["read"], mine)]
+        nh = sm["n_hits"].astype(np.int64)
+        first = np.repeat(sm["hit_off"].astype(np.int64) - np.concatenate(([0], np.cumsum(nh)[:-1])), nh)
+        sh = h[first + np.arange(int(nh.sum()), dtype=np.int64)]
+        self.parts[j] = (np.stack([sm["read"] + float(base), sm["ctg"], sm["n_hits"]], axis=1),
+                         np.stack([np.repeat(sm["read"] + float(base), nh), np.repeat(sm["ctg"], nh), sh["ctg_pos"], sh["read_pos"],
+                                   sh["ctg_strand"], sh["read_strand"]], axis=1),
+                         np.stack([sp["read"] + float(base), sp["ctg"], sp["q_start"], sp["q_end"], sp["t_start"], sp["t_end"], sp["n_hits"],
+                                   sp["strand"]], axis=1))
+
+    def arrays(self):
+        import numpy as np
+        if any(x is None for x in self.counts) or sorted(self.parts) != self.held:
+            raise RuntimeError("--dump-outputs: a sub-batch's result was not taken")
+        out = {"counts": np.array(self.counts, np.float64)}
+        for i, nm in enumerate(("maps", "hits", "pafs")):
+            out[nm] = np.concatenate([self.parts[j][i] for j in self.held]).astype(np.float64)
+        room = DUMP_MAX_BYTES - sum(a.nbytes for nm, a in out.items() if nm != "hits")
+        if out["hits"].nbytes > room:
+            out["hits"] = out["hits"][:max(0, room // (8 * out["hits"].shape[1]))]
+        return out
+
+
+def write_outputs(outputs, path):
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    for nm, a in outputs.items():
+        np.save(os.path.join(path, nm + ".npy"), a)
+    print(f"bench: outputs of the step in {path}: " + ", ".join(f"{nm} {a.shape}" for nm, a in outputs.items()), file=sys.stderr)
 
 
 def summarize(R, args, world, dev_name):
@@ -556,7 +684,9 @@ def main():
     comm = Comm(use_cuda, local_rank)
     dev = capi.Device(local_rank if use_cuda else 0, lib_path=args.lib)
 
-    R = run_workload(dev, comm, args.workload, args, args.steps, args.warmup, rank, world, args.serial_steps)
+    R = run_workload(dev, comm, args.workload, args, args.steps, args.warmup, rank, world, args.serial_steps, dump=bool(args.dump_outputs) and rank == 0)
+    if R["outputs"] is not None:
+        write_outputs(R["outputs"], args.dump_outputs)
     if rank == 0:
         value, ms_per_step, cfg, roof = summarize(R, args, world, dev.name)
         out = {
@@ -577,16 +707,16 @@ def main():
         if cores_mine:
             out["cores_per_rank"] = cores_mine
             out["pin_rank0"] = dict(LAST_PIN)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dev, R["wl"], R["W"], R["params"])
-        if world == 1 and not args.no_e2e and use_cuda:
+        if world == 1 and args.full and not args.no_e2e and use_cuda:
             for h in R["wl"].read_batches:
                 h.close()
             R["wl"].read_batches = []
             with stdout_to_stderr():  # the driver logs its steps on stdout as the reference does (bin/ntlink_pair.py:540-606); stdout is the JSON line's
                 out["end_to_end"] = end_to_end(dev, R["wl"], R["W"], args)
     R["ix"].close(); R["csk"].close(); R["wl"].close()
-    if world == 1 and rank == 0 and not args.no_others and args.scale == 1.0:
+    if world == 1 and rank == 0 and args.full and not args.no_others and args.scale == 1.0:
         # the other single-GPU configurations of BASELINE.json under the same clock (fewer steps; same definitions)
         others = {}
         for name, st in (("C2", 200), ("C5", 3)):

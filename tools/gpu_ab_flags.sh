@@ -13,7 +13,7 @@ for V in default flags; do
   python __graft_entry__.py > $O/build_$V.log 2>&1 || { tail -20 $O/build_$V.log; exit 1; }
   timeout 600 python -m pytest tests -m gpu -x -q -k strip_lists 2>&1 | tail -2
   for W in $WL; do
-    timeout 600 python bench.py --workload $W --steps 8 --warmup 2 --no-cpu-baseline --no-e2e --no-others > $O/bench_${W}_$V.json 2> $O/bench_${W}_$V.err
+    timeout 600 python bench.py --workload $W --steps 8 --warmup 2 --full --no-cpu-baseline --no-e2e --no-others > $O/bench_${W}_$V.json 2> $O/bench_${W}_$V.err
     python - <<PY
 import json
 d=json.load(open("$O/bench_${W}_$V.json")); c=d["config"]; r=d["roofline"]

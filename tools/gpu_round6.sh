@@ -1,5 +1,5 @@
 #!/bin/bash
-# One GPU-box visit (rounds 4-6): build, all gpu tests, smoke, the default bench line (C3 pipelined + serial pass + C2/C5 +
+# One GPU-box visit (rounds 4-6): build, all gpu tests, smoke, the full bench line (--full: C3 pipelined + serial pass + C2/C5 +
 # cpu baseline + end to end), a single-rank torch.distributed.run line, then -- with NTL_PIPELINE=0, so that per-kernel
 # figures are those of kernels running alone -- rocprofv3 kernel trace + three PMC passes per workload, each in its own run.
 # usage: tools/gpu_round5.sh <tag> [workloads to profile, default "C3 C5 C2"]   (SKIP_TESTS / SKIP_TORCHRUN / SKIP_PROF / SKIP_BENCH=1)
@@ -16,7 +16,7 @@ timeout 1800 python -m pytest tests -m gpu -x -q 2>&1 | tail -15 | tee $O/pytest
 timeout 300 python __graft_entry__.py smoke 2>&1 | tail -2 | tee $O/smoke.log
 fi
 if [ -z "$SKIP_BENCH" ]; then
-timeout 1500 python bench.py $BENCH_ARGS > $O/bench.json 2> $O/bench.err
+timeout 1500 python bench.py --full $BENCH_ARGS > $O/bench.json 2> $O/bench.err
 head -c 1500 $O/bench.json; echo; tail -5 $O/bench.err
 fi
 if [ -z "$SKIP_TORCHRUN" ]; then

@@ -15,7 +15,7 @@ for V in default $VARIANTS; do
   fi
   if [ -n "$TESTS" ]; then timeout 900 bash -c "python -m pytest tests -m gpu -x -q $TESTS" 2>&1 | tail -3; fi
   for W in $WL; do
-    timeout 600 python bench.py --workload $W --steps ${STEPS:-6} --warmup 2 --no-cpu-baseline --no-e2e --no-others > $O/bench_${W}_$V.json 2> $O/bench_${W}_$V.err
+    timeout 600 python bench.py --workload $W --steps ${STEPS:-6} --warmup 2 --full --no-cpu-baseline --no-e2e --no-others > $O/bench_${W}_$V.json 2> $O/bench_${W}_$V.err
     python - <<PY
 import json
 try:
