@@ -17,6 +17,27 @@
 #define NTL_NONE 0xFFFFFFFFu
 #define NTL_LEAD_PAD 16u /* bases of padding in front of the first sequence of a batch */
 
+/* A size or a sum for the host: a vector store from the calling lane into a handle's page-locked slot (coherent, mapped host
+ * memory, ntl_ctx_create).  System scope: the write goes to host memory, not into a cache of this device.  The host reads the
+ * slot only after the handle's event, recorded on the stream behind the writing kernel, has passed: the end-of-kernel release
+ * and that event order the write before the read. */
+__device__ __forceinline__ void ntl_host_store32(uint32_t *p, uint32_t v)
+{
+#ifdef NTL_SIM
+    *p = v;
+#else
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#endif
+}
+__device__ __forceinline__ void ntl_host_store64(unsigned long long *p, unsigned long long v)
+{
+#ifdef NTL_SIM
+    *p = v;
+#else
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+#endif
+}
+
 /* srol / sror on the two 32-bit halves (lo = bits 0..31, hi bit 0 = bit 32 of the 33-bit ring, hi bits 1..31 = the
  * 31-bit ring): 5 and 4 VALU instructions, every one written out (v_alignbit / v_bfi / v_lshl_or) */
 __device__ __forceinline__ uint64_t srol1(uint64_t x)

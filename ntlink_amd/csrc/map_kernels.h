@@ -182,7 +182,6 @@ struct MapArgs {
     uint64_t scr_stride;
     uint32_t *err;
     uint32_t *over_list, *over_count;             /* reads that do not fit the LDS staging: [nreads], [1] */
-    uint32_t *nmx_out;                            /* [1] the batch's number of read minimizers, for the host's hit fraction */
     /* The sketch may still be in flight when these kernels are queued (nothing waits on the host for its size): when its
        minimizer total turns out larger than the arrays that were sized from the expected density, the records are incomplete
        and every kernel here leaves the batch alone; the host makes the sketch again and queues the map a second time. */
@@ -711,12 +710,33 @@ __global__ __launch_bounds__(MAP_NT) NTL_MAIN_STREAM_SGPRS void map_overflow_ker
    device reaches the hits through hit_off (the text kernels, the tally's first / last hits), and copying 12 bytes per hit a
    second time was most of this kernel (C5: 0.85 GB read + 0.85 GB written per sub-batch, 0.33 ms of it).  ntl_mapres_download
    makes the dense copy it hands to the host when it is asked (map_densify_kernel). */
-__global__ void map_gather_kernel(MapArgs A, const uint32_t *off_maps, const uint32_t *off_pafs, MapRec *d_maps, PafRec *d_pafs)
+/* A map result's sums.  The device copy is the result's entry of the context's per-slot array (ntl_hip.hip map_enqueue), zero
+   whenever the slot is free: the scans store tot[], the map kernels add to err / n_over, probe_kernel to nfound.  The host's copy
+   is the result's page-locked slot, same layout (the zombie checks read w[1] low = err, w[3] high = nmx). */
+struct MapSums { unsigned long long nfound; uint32_t err; uint32_t tot[3]; uint32_t n_over; uint32_t nmx; };
+struct MapSumsOut {
+    MapSums *sums;                      /* the device copy: read, and left zero for the next holder of the slot */
+    const unsigned long long *nfound;   /* the lookup's hit count: &sums->nfound, or the read sketch's own (SketchSums) */
+    unsigned long long *slot;           /* the result's page-locked slot (device view), 4 words */
+    unsigned long long *sk_nfound;      /* not NULL: the read sketch's slot word for its hit count, too */
+};
+
+__global__ void map_gather_kernel(MapArgs A, const uint32_t *off_maps, const uint32_t *off_pafs, MapRec *d_maps, PafRec *d_pafs, MapSumsOut O)
 {
-    if (map_sketch_overflowed(A)) return;
     const uint32_t r = blockIdx.x;
+    if (r == 0 && threadIdx.x == 0) { /* every kernel that writes the sums ran before this one */
+        MapSums *d = O.sums;
+        const unsigned long long nf = *O.nfound;
+        const uint32_t nmx = map_sketch_overflowed(A) ? 0u : A.mx_off[A.nreads]; /* (an overflowed sketch: no hit fraction) */
+        ntl_host_store64(O.slot, nf);
+        ntl_host_store64(O.slot + 1, (unsigned long long)d->err | ((unsigned long long)d->tot[0] << 32));
+        ntl_host_store64(O.slot + 2, (unsigned long long)d->tot[1] | ((unsigned long long)d->tot[2] << 32));
+        ntl_host_store64(O.slot + 3, (unsigned long long)d->n_over | ((unsigned long long)nmx << 32));
+        if (O.sk_nfound) ntl_host_store64(O.sk_nfound, nf);
+        d->nfound = 0ull; d->err = 0u; d->tot[0] = d->tot[1] = d->tot[2] = 0u; d->n_over = 0u; d->nmx = 0u;
+    }
+    if (map_sketch_overflowed(A)) return;
     const uint32_t m0 = A.mx_off[r];
-    if (r == 0 && threadIdx.x == 0) *A.nmx_out = A.mx_off[A.nreads];
     const uint32_t nm = A.n_maps[r], npf = A.n_pafs[r];
     const uint32_t om = off_maps[r], op = off_pafs[r];
     for (uint32_t i = threadIdx.x; i < nm; i += blockDim.x) {

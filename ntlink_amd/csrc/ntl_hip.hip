@@ -82,6 +82,7 @@ struct Zombie {
     uint64_t cap = 0;
     std::shared_ptr<std::atomic<float>> hitf; /* 2: where the batch's hit fraction goes (MapSums: nfound / nmx) */
     const struct ntl_index *ix = nullptr; /* the index the queued kernels read: its reference is dropped when they have run */
+    const struct ntl_batch *batch = nullptr; /* 2: the batch whose lengths the map kernels read (d_seq_len): likewise */
 };
 
 struct ntl_ctx {
@@ -127,6 +128,8 @@ struct ntl_ctx {
     void *host_tmp = nullptr;           /* page-locked bounce buffer for record downloads (grows, never shrinks) */
     size_t host_tmp_cap = 0;
     PinSlot *slots = nullptr;
+    PinSlot *slots_dev = nullptr;       /* the same slots as the kernels address them (mapped: the kernels write sizes and sums there) */
+    PinSlot *dslots = nullptr;          /* device memory, one entry per slot: a map result's sums (MapSums), zero while the slot is free */
     std::vector<uint32_t> slot_free;
     std::deque<Zombie> zombies;
     hipEvent_t throttle[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
@@ -269,6 +272,10 @@ static hipError_t main_wait(ntl_ctx *c)
 
 static PinSlot *slot_get(ntl_ctx *c);
 static void index_unref(const struct ntl_index *ix, ntl_ctx *by);
+static void batch_unref(const struct ntl_batch *b);
+/* a slot as the kernels address it, and its entry of the device-side array */
+static PinSlot *slot_dev(const ntl_ctx *c, const PinSlot *p) { return c->slots_dev + (p - c->slots); }
+static PinSlot *slot_dsums(const ntl_ctx *c, const PinSlot *p) { return c->dslots + (p - c->slots); }
 static void slot_put(ntl_ctx *c, PinSlot *p) { if (p) c->slot_free.push_back((uint32_t)(p - c->slots)); }
 
 /* zombies whose work has finished: check what they carried, recycle event and slot.  block: wait for the oldest one. */
@@ -296,6 +303,7 @@ static void reap(ntl_ctx *c, bool block)
         sev_put(c, z.done);
         slot_put(c, z.slot);
         index_unref(z.ix, c);
+        batch_unref(z.batch);
         c->zombies.pop_front();
     }
 }
@@ -678,7 +686,24 @@ extern "C" int ntl_ctx_create(int device, ntl_ctx **out)
             delete c;
             return NTL_EDEVICE;
         }
+        /* Kernels write the sizes and sums that come back to the host straight into the slots (ntl_host_store32/64): the slots are
+           mapped into the device's address space and coherent (fine-grained: a device store goes to host memory, not into the
+           device's L2), whatever HIP_HOST_COHERENT says -- hipHostMallocDefault leaves coherence to that variable. */
+#ifdef NTL_SIM
         if (hipHostMalloc((void **)&c->slots, NTL_NSLOTS * sizeof(PinSlot), hipHostMallocDefault) != hipSuccess) {
+            delete c;
+            return NTL_EDEVICE;
+        }
+        c->slots_dev = c->slots;
+#else
+        if (hipHostMalloc((void **)&c->slots, NTL_NSLOTS * sizeof(PinSlot), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
+            hipHostGetDevicePointer((void **)&c->slots_dev, c->slots, 0) != hipSuccess) {
+            delete c;
+            return NTL_EDEVICE;
+        }
+#endif
+        if (hipMalloc((void **)&c->dslots, NTL_NSLOTS * sizeof(PinSlot)) != hipSuccess ||
+            hipMemset(c->dslots, 0, NTL_NSLOTS * sizeof(PinSlot)) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
             delete c;
             return NTL_EDEVICE;
         }
@@ -728,6 +753,7 @@ extern "C" void ntl_ctx_destroy(ntl_ctx *c)
     c->slabs.clear();
     if (c->host_tmp) pin_free(c->host_tmp);
     if (c->slots) (void)hipHostFree(c->slots);
+    if (c->dslots) (void)hipFree(c->dslots);
     for (auto &kv : c->profs)
         for (auto &sp : kv.second.spans) { (void)hipEventDestroy(sp.first); (void)hipEventDestroy(sp.second); }
     for (auto e : c->ev_free) (void)hipEventDestroy(e);
@@ -1287,8 +1313,10 @@ struct ntl_sketch {
     mutable bool from_lists = false; /* diagnostics: the last round of sketch_enqueue wrote lists */
     mutable bool no_lists = false; /* the window stage writes the bitmask whatever the window: the second round of a sketch whose lists ran out of pool */
     mutable DevBuf rpos;    /* u32[cap] beside cand: the minimizers' positions in their reads (their strands: bit 31 of Cand::meta) */
-    mutable DevBuf rlen;    /* u32[nseq]: lengths of the sketched sequences (sketches made from a batch) */
     mutable DevBuf sums;    /* SketchSums on the device: total (read by the map kernels: a sketch that overflowed its arrays is left alone) */
+    /* the lookup's hit count has not reached the slot yet: the next kernel queued behind the lookup on MAIN copies it there -- the
+       gather of the first map result on this sketch (map_enqueue), or sketch_nfound_kernel when the count is asked for first */
+    mutable bool nfound_owed = false;
     /* lazy completion */
     mutable bool pending = false;
     mutable hipEvent_t done = nullptr;
@@ -1693,9 +1721,10 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     if ((rc = run_n.alloc(c, (b->nruns + 1) * 4, psid)) || (rc = run_ord.alloc(c, (b->nruns + 1) * 4, psid)) ||
         (rc = seq_M.alloc(c, (nseq + 1) * 4, psid)) || (rc = nstrips.alloc(c, (nseq + 1) * 4, psid)) ||
         (rc = strip_first.alloc(c, (nseq + 2) * 4, psid)) || (rc = s->mx_off.alloc(c, (nseq + 1) * 4)) ||
-        (rc = s->sums.alloc(c, sizeof(SketchSums)))) {
+        (rc = s->sums.alloc(c, sizeof(SketchSums), psid))) {
         return rc;
     }
+    s->sums.touch(SID_MAIN); /* zeroed by strip_table_kernel on the preparation's stream, added to and read on MAIN */
     batch_on_wstream(c, b);
     SeqTables T;
     T.packed = b->packed.as<uint32_t>(); T.seq_base = b->seq_base.as<uint64_t>();
@@ -1781,7 +1810,10 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     if ((rc = strip_lite.alloc(c, (ub_strips + 1) * sizeof(StripLite), psid))) return rc;
     run_n.touch(SID_W); run_ord.touch(SID_W); seq_M.touch(SID_W); strip_tab.touch(SID_W); strip_lite.touch(SID_W);
     SketchSums *dsums = s->sums.as<SketchSums>();
-    HIPCHK(c, hipMemsetAsync(dsums, 0, sizeof(SketchSums), ms));
+    /* the device sums are zeroed by strip_table_kernel (StripZero); every kernel that writes them runs on MAIN behind the window
+       stage, which waits for the preparation (the events below; one stream when the pipeline is off).  No sequence, no kernel: a fill */
+    Z.sums = (uint32_t *)dsums; Z.nsums = (uint32_t)(sizeof(SketchSums) / 4);
+    if (!nseq) HIPCHK(c, hipMemsetAsync(dsums, 0, sizeof(SketchSums), ms));
     {
         ProfSpan sp(c, "sketch_meta", psid);
         if (nseq) {
@@ -1814,7 +1846,7 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
         make_tables(k, A.roll_tab, A.seed_tab);
         A.g4 = (const uint64_t (*)[2])c->g4;
         A.g8 = (const uint64_t (*)[2])c->g8;
-        A.redo_list = nullptr; A.redo_count = nullptr;
+        A.redo_list = nullptr; A.redo_count = nullptr; A.redo_out = nullptr;
         A.Ls = Ls;
         if (fast) {
             B.A = A;
@@ -1854,11 +1886,12 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
             ProfSpan sp(c, "sketch_redo", wsid);
             SketchArgs R = A;
             R.redo_count = B.redo_count; R.redo_list = B.redo_list;
+            /* the redo pass writes the two counts into the slot (`redo` never leaves the window stream); s->done, on MAIN behind the
+               emit kernel, is behind it too (window stage -> emit) */
+            R.redo_out = &((SketchSums *)slot_dev(c, s->slot))->redo_n;
             launch_mask<16>(c, R, (unsigned)ub_strips, true, false, nt);
             if (b->any_multi) launch_mask<16>(c, A, (unsigned)ub_strips, false, true, nt);
             HIPCHK(c, hipGetLastError());
-            /* the redo count travels with the window stream: `redo` never leaves it */
-            HIPCHK(c, hipMemcpyAsync(&((SketchSums *)s->slot)->redo_n, redo.p, 8, hipMemcpyDeviceToHost, ws));
         } else {
             ProfSpan sp(c, "sketch_mask", wsid);
             if (small) launch_small_w<2>(c, A, (unsigned)ub_strips, b->any_multi);
@@ -1885,7 +1918,9 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
                kernels leave such a sketch alone and sketch_finalize makes it again through the bitmask) */
             strip_first.touch(SID_MAIN); strip_tab.touch(SID_MAIN);
             if ((rc = device_scan(c, Ls.cnt, loff.as<uint32_t>(), ub_strips, nullptr, 1, &dsums->total_mx))) return rc;
-            hipLaunchKernelGGL(list_fail_kernel, dim3(1), dim3(64), 0, ms, (const uint32_t *)Ls.ctl, &dsums->total_mx, &dsums->list_fail, tile_next.as<uint32_t>());
+            SketchSums *hd = (SketchSums *)slot_dev(c, s->slot); /* the true total and whether the lists ran out, for the host */
+            hipLaunchKernelGGL(list_fail_kernel, dim3(1), dim3(64), 0, ms, (const uint32_t *)Ls.ctl, &dsums->total_mx, &dsums->list_fail, tile_next.as<uint32_t>(),
+                               &hd->total_mx, &hd->list_fail);
             hipLaunchKernelGGL(mx_off_from_strips_kernel, dim3((unsigned)((nseq + 256) / 256)), dim3(256), 0, ms, (const uint32_t *)strip_first.as<uint32_t>(),
                                (const uint32_t *)loff.as<uint32_t>(), (uint32_t)nseq, s->mx_off.as<uint32_t>());
         } else {
@@ -1971,18 +2006,13 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
             c->masks.push_back(mask);
             mask.p = nullptr; /* handed over */
         }
-        /* lengths of the sketched sequences for the map kernels (the batch may be gone by then) */
-        if (b->d_seq_len && nseq && !s->rlen.p) { /* (a second round keeps the array of the first: ntl_map_run may hold its address already) */
-            if ((rc = s->rlen.alloc(c, nseq * 4))) return rc;
-            HIPCHK(c, hipMemcpyAsync(s->rlen.p, b->d_seq_len, nseq * 4, hipMemcpyDeviceToDevice, ms));
-        }
-        SketchSums *hs = (SketchSums *)s->slot;
-        if (lists) { /* the true total (the device's copy says "too many" when the lists ran out), and whether they did */
-            HIPCHK(c, hipMemcpyAsync(&hs->total_mx, loff.as<uint32_t>() + ub_strips, 4, hipMemcpyDeviceToHost, ms));
-            HIPCHK(c, hipMemcpyAsync(&hs->list_fail, &dsums->list_fail, 4, hipMemcpyDeviceToHost, ms));
-        } else
-        HIPCHK(c, hipMemcpyAsync(&hs->total_mx, &dsums->total_mx, 4, hipMemcpyDeviceToHost, ms));
-        if (ix) HIPCHK(c, hipMemcpyAsync(&hs->nfound, &dsums->nfound, 8, hipMemcpyDeviceToHost, ms));
+        /* (the map kernels read the lengths of the sketched sequences from the batch itself: ntl_map_run holds it) */
+        s->nfound_owed = false;
+        if (!lists) { /* the bitmask path (off the hot path): the totals come back by copies */
+            SketchSums *hs = (SketchSums *)s->slot;
+            HIPCHK(c, hipMemcpyAsync(&hs->total_mx, &dsums->total_mx, 4, hipMemcpyDeviceToHost, ms));
+            if (ix) HIPCHK(c, hipMemcpyAsync(&hs->nfound, &dsums->nfound, 8, hipMemcpyDeviceToHost, ms));
+        } else s->nfound_owed = ix != nullptr; /* (list_fail_kernel wrote the total and the flag) */
     }
     HIPCHK(c, hipEventRecord(s->done, ms));
     {
@@ -2042,6 +2072,14 @@ static int sketch_finalize(const ntl_sketch *cs)
     ntl_ctx *c = s->c;
     (void)hipSetDevice(c->device);
     for (int round = 0;; round++) {
+        if (s->nfound_owed) { /* no map kernel took the hit count: a kernel of its own, behind the lookup, and the event behind that */
+            s->nfound_owed = false;
+            hipLaunchKernelGGL(sketch_nfound_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long *)&s->sums.as<SketchSums>()->nfound,
+                               &((SketchSums *)slot_dev(c, s->slot))->nfound);
+            hipError_t le = hipGetLastError();
+            if (le == hipSuccess) le = hipEventRecord(s->done, c->stream);
+            if (le != hipSuccess) { (void)sync_both(c); s->pending = false; s->failed = fail(c, NTL_EDEVICE, std::string("sketch: ") + hipGetErrorString(le)); break; }
+        }
         const hipError_t e = wait_hot(s->done);
         s->pending = false;
         if (e != hipSuccess) { s->failed = fail(c, NTL_EDEVICE, std::string("sketch: ") + hipGetErrorString(e)); break; }
@@ -2334,8 +2372,7 @@ extern "C" uint64_t ntl_index_size(const ntl_index *ix)
 
 /* ------------------------------------------------------------------ map ------------------ */
 
-struct MapSums { unsigned long long nfound; uint32_t err; uint32_t tot[3]; uint32_t n_over; uint32_t nmx; }; /* one memset, one read-back */
-static_assert(sizeof(MapSums) <= sizeof(PinSlot), "the sums must fit a page-locked slot");
+static_assert(sizeof(MapSums) <= sizeof(PinSlot), "the sums must fit a page-locked slot (map_kernels.h)");
 
 struct ntl_mapres {
     ntl_ctx *c;
@@ -2355,6 +2392,8 @@ struct ntl_mapres {
     ntl_map_params params;
     std::shared_ptr<std::atomic<float>> hitf; /* the index's hit fraction (the index itself may be gone when this completes) */
     DevBuf rlen_own;                    /* read lengths uploaded by this call (sketches that did not come from a batch) */
+    const uint32_t *d_rlen = nullptr;   /* the read lengths the kernels read: rlen_own, or the batch's own (d_seq_len) */
+    const ntl_batch *batch = nullptr;   /* ... whose batch is held (refs) until the kernels have run */
 };
 
 /* Queues the lookup (when the sketch does not carry candidates), the map kernels, the offset scans and the gather on MAIN.
@@ -2371,20 +2410,22 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
     const ntl_map_params *params = &R->params;
     int rc;
     hipStream_t ms = c->stream;
-    DevBuf cand, rpos, smaps, spafs, n3, off3, scr, sums, over;
+    DevBuf cand, rpos, smaps, spafs, n3, off3, scr, over;
     R->dense_made = R->doff_made = false;
     const uint64_t cap = nmx ? nmx : 1;
     if ((!have_cand && ((rc = cand.alloc(c, cap * sizeof(Cand))) || (rc = rpos.alloc(c, cap * 4)))) ||
         (rc = smaps.alloc(c, cap * sizeof(MapRec))) ||
         (rc = spafs.alloc(c, cap * sizeof(PafRec))) || (rc = n3.alloc(c, 3 * (nreads + 1) * 4)) ||
         (rc = off3.alloc(c, 3 * (nreads + 1) * 4)) || (rc = scr.alloc(c, (uint64_t)(MAP_NHA + MAP_NRA) * cap * 4)) ||
-        (rc = sums.alloc(c, sizeof(MapSums))) || (rc = over.alloc(c, (nreads + 1) * 4)) ||
+        (rc = over.alloc(c, (nreads + 1) * 4)) ||
         (rc = R->maps.alloc(c, cap * sizeof(MapRec))) || (rc = R->hits.alloc(c, cap * sizeof(HitRec))) ||
         (rc = R->pafs.alloc(c, cap * sizeof(PafRec)))) return rc;
-    MapSums *dsums = sums.as<MapSums>();
+    /* The sums: the result's entry of the per-slot device array.  It is zero whenever the slot is free -- map_gather_kernel, the last
+       kernel of this work, hands the sums to the slot and leaves the entry zero; the slot is recycled only after R->done, behind it
+       (or, on the error paths, after map_scrub) -- and every kernel that adds to it runs on MAIN behind the gather of the slot's
+       previous holder.  The lookup's count of a sketch made for this index stays where the lookup left it (SketchSums::nfound). */
+    MapSums *dsums = (MapSums *)slot_dsums(c, R->slot);
     if (ix->c != c && ix->built) HIPCHK(c, hipStreamWaitEvent(ms, ix->built, 0));
-    HIPCHK(c, hipMemsetAsync(sums.p, 0, sizeof(MapSums), ms));
-    if (have_cand) HIPCHK(c, hipMemcpyAsync(&dsums->nfound, &reads->sums.as<SketchSums>()->nfound, 8, hipMemcpyDeviceToDevice, ms));
     if (!have_cand) {
         ProfSpan sp(c, "probe");
         if (nmx) {
@@ -2414,7 +2455,6 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
     A.n_maps = n3.as<uint32_t>(); A.n_hits = A.n_maps + (nreads + 1); A.n_pafs = A.n_hits + (nreads + 1);
     A.scr = scr.as<uint32_t>(); A.scr_stride = cap; A.err = &dsums->err;
     A.over_list = over.as<uint32_t>(); A.over_count = &dsums->n_over;
-    A.nmx_out = &dsums->nmx;
     /* a sketch whose count is not known yet may have overflowed its arrays: the kernels look at its total and leave it alone */
     A.mx_total = reads->pending ? &reads->sums.as<SketchSums>()->total_mx : nullptr;
     A.mx_cap = (uint32_t)std::min<uint64_t>(reads->cap, 0xFFFFFFFFull);
@@ -2439,15 +2479,32 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
         ProfSpan sp(c, "compact");
         uint32_t *o = off3.as<uint32_t>();
         if ((rc = device_scan(c, n3.as<uint32_t>(), o, nreads, nullptr, 3, dsums->tot))) return rc;
+        MapSumsOut O;
+        O.sums = dsums;
+        O.nfound = have_cand ? &reads->sums.as<SketchSums>()->nfound : &dsums->nfound;
+        O.slot = (unsigned long long *)slot_dev(c, R->slot);
+        /* the sketch's own hit count, if nothing has copied it yet: its event moves behind this kernel (sketch_finalize waits for it) */
+        O.sk_nfound = nullptr;
+        if (have_cand && reads->pending && reads->nfound_owed) O.sk_nfound = &((SketchSums *)slot_dev(c, reads->slot))->nfound;
         hipLaunchKernelGGL(map_gather_kernel, dim3((unsigned)nreads), dim3(64), 0, ms, A, (const uint32_t *)o,
-                           (const uint32_t *)(o + 2 * (nreads + 1)), R->maps.as<MapRec>(), R->pafs.as<PafRec>());
+                           (const uint32_t *)(o + 2 * (nreads + 1)), R->maps.as<MapRec>(), R->pafs.as<PafRec>(), O);
         HIPCHK(c, hipGetLastError());
+        if (O.sk_nfound) {
+            HIPCHK(c, hipEventRecord(reads->done, ms));
+            reads->nfound_owed = false;
+        }
     }
-    HIPCHK(c, hipMemcpyAsync(R->slot, sums.p, sizeof(MapSums), hipMemcpyDeviceToHost, ms));
+    /* (no reads: no kernel, and the slot keeps the zeros slot_get left in it) */
     HIPCHK(c, hipEventRecord(R->done, ms));
     R->pending = true;
     R->reads_gen = reads->gen;
     return NTL_OK;
+}
+
+/* an error path left the result's device sums in an unknown state (the device is idle: sync_both): zero again for the slot's next holder */
+static void map_scrub(ntl_ctx *c, const ntl_mapres *R)
+{
+    if (R->slot) (void)hipMemset(slot_dsums(c, R->slot), 0, sizeof(PinSlot));
 }
 
 static void mapres_free(ntl_mapres *R)
@@ -2457,12 +2514,13 @@ static void mapres_free(ntl_mapres *R)
     (void)hipSetDevice(c->device);
     if (R->pending) {
         Zombie z;
-        z.done = R->done; z.slot = R->slot; z.kind = 2; z.hitf = R->hitf; z.ix = R->ix;
+        z.done = R->done; z.slot = R->slot; z.kind = 2; z.hitf = R->hitf; z.ix = R->ix; z.batch = R->batch;
         c->zombies.push_back(z);
     } else {
         sev_put(c, R->done);
         slot_put(c, R->slot);
         index_unref(R->ix, c);
+        batch_unref(R->batch);
     }
     if (R->reads) sketch_unref(R->reads);
     delete R;
@@ -2483,8 +2541,8 @@ static int mapres_finalize(const ntl_mapres *cR)
         if (e != hipSuccess) { R->failed = fail(c, NTL_EDEVICE, std::string("map: ") + hipGetErrorString(e)); break; }
         if (R->reads && R->reads->gen != R->reads_gen && round == 0) {
             memset(R->slot, 0, sizeof(PinSlot));
-            const int rc = map_enqueue(c, R->ix, R->reads, R->rlen_own.p ? R->rlen_own.as<uint32_t>() : R->reads->rlen.as<uint32_t>(), R);
-            if (rc) { (void)sync_both(c); R->pending = false; R->failed = rc; break; }
+            const int rc = map_enqueue(c, R->ix, R->reads, R->d_rlen, R);
+            if (rc) { (void)sync_both(c); map_scrub(c, R); R->pending = false; R->failed = rc; break; }
             continue;
         }
         const MapSums hs = *(const MapSums *)R->slot;
@@ -2496,6 +2554,7 @@ static int mapres_finalize(const ntl_mapres *cR)
     }
     if (R->reads) { sketch_unref(R->reads); R->reads = nullptr; }
     index_unref(R->ix, c); R->ix = nullptr;
+    batch_unref(R->batch); R->batch = nullptr;
     sev_put(c, R->done); R->done = nullptr;
     slot_put(c, R->slot); R->slot = nullptr;
     return R->failed;
@@ -2519,13 +2578,14 @@ extern "C" int ntl_map_run(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *re
     R->slot = slot_get(c);
     if (!R->done || !R->slot) { mapres_free(R); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
     int rc = NTL_OK;
-    /* read lengths: a sketch made from a batch has them on the device already (the `--len` column IS the sequence length);
-       anything else -- or lengths that differ from the batch's -- is uploaded here */
+    /* read lengths: a sketch made from a batch that it still holds (pending) reads them from the batch (the `--len` column IS the
+       sequence length); the result holds the batch too, until its kernels have run (mapres_finalize, or reap for a result destroyed
+       before that).  Anything else -- or lengths that differ from the batch's -- is uploaded here. */
     const uint32_t *d_rlen = nullptr;
-    if (reads->rlen.p && nreads) {
-        /* the device copy was made from the batch; the caller's array is checked against it on the host side of the batch */
-        d_rlen = reads->rlen.as<uint32_t>();
-        if (!reads->src || memcmp(read_len, reads->src->seq_len.data(), nreads * 4) != 0) d_rlen = nullptr;
+    if (reads->src && reads->src->d_seq_len && nreads && memcmp(read_len, reads->src->seq_len.data(), nreads * 4) == 0) {
+        d_rlen = reads->src->d_seq_len;
+        const_cast<ntl_batch *>(reads->src)->refs++;
+        R->batch = reads->src;
     }
     if (!d_rlen) {
         if ((rc = R->rlen_own.alloc(c, (nreads + 1) * 4))) { mapres_free(R); return rc; }
@@ -2538,10 +2598,12 @@ extern "C" int ntl_map_run(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *re
         }
         d_rlen = R->rlen_own.as<uint32_t>();
     }
+    R->d_rlen = d_rlen;
     const_cast<ntl_sketch *>(reads)->refs++;
     R->reads = reads;
     if ((rc = map_enqueue(c, ix, reads, d_rlen, R))) {
         (void)sync_both(c);
+        map_scrub(c, R);
         R->pending = false;
         mapres_free(R);
         return rc;

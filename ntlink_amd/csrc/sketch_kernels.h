@@ -152,10 +152,11 @@ __device__ __forceinline__ void strip_bits_to_list(const StripLists &Ls, uint32_
 
 /* what the window passes count into, zeroed here (one thread per word) instead of by fills of their own: the strips' minimizer counts
    with the lists' two control words behind them, and the head of the fast pass's buffer (its two counters and sketch_wave_kernel's
-   chunk counters) */
+   chunk counters), and the sketch's device sums (SketchSums: the lookup's hit count is added to them on MAIN, behind this kernel) */
 struct StripZero {
     uint32_t *cnt; uint32_t ncnt;
     uint32_t *head; uint32_t nhead;
+    uint32_t *sums; uint32_t nsums;
 };
 
 __global__ void strip_table_kernel(SeqTables T, const uint32_t *run_n, const uint32_t *run_ord, const uint32_t *seq_M,
@@ -165,6 +166,7 @@ __global__ void strip_table_kernel(SeqTables T, const uint32_t *run_n, const uin
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; /* one thread per strip */
     for (uint32_t j = i; j < Z.ncnt; j += gridDim.x * blockDim.x) Z.cnt[j] = 0u;
     if (i < Z.nhead) Z.head[i] = 0u;
+    if (i < Z.nsums) Z.sums[i] = 0u;
     if (i >= cap) return;
     if (i >= strip_first[T.nseq]) { /* the grid of the sketch kernel is an upper bound */
         tab[i].seq = NTL_NONE;
@@ -220,6 +222,7 @@ struct SketchArgs {
     const struct StripLite *strip_lite; /* [nstrips + 1] the same for sketch_wave_kernel */
     const uint32_t *redo_list;   /* not NULL: process exactly these strips (flagged by sketch_fast_kernel), looping */
     const uint32_t *redo_count;
+    uint32_t *redo_out;          /* with redo_list: the host's copy of the fast pass's two counts (its sketch's slot: redo_n, fb_n), or NULL */
     StripLists Ls;               /* Ls.cnt != NULL: the strips' minimizers go to their lists, not to the bitmask */
 };
 
@@ -483,6 +486,10 @@ __global__ __launch_bounds__(NT) void sketch_mask_kernel(SketchArgs A)
 {
     if (A.redo_list) { /* the exact pass over the strips sketch_fast_kernel could not decide */
         const uint32_t n = *A.redo_count;
+        if (A.redo_out && blockIdx.x == 0 && threadIdx.x == 0) { /* both counts are final: every kernel that adds to them ran before this one */
+            ntl_host_store32(A.redo_out, n);
+            ntl_host_store32(A.redo_out + 1, A.redo_count[1]);
+        }
         for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
             sketch_mask_strip<C, NT, MULTI, R0T>(A, A.redo_list[i]);
             __syncthreads(); /* the strip's LDS arrays are reused */
@@ -793,14 +800,23 @@ struct EmitListArgs {
 
 /* behind the scan of the strips' counts: a sketch whose lists ran out of pool carries a total that no array holds (the map kernels
    leave it alone, map_sketch_overflowed) and the flag that tells sketch_finalize why; also zeroes the emit kernel's tile counters */
-__global__ void list_fail_kernel(const uint32_t *__restrict__ ctl, uint32_t *__restrict__ total, uint32_t *__restrict__ flag, uint32_t *__restrict__ tile_next)
+__global__ void list_fail_kernel(const uint32_t *__restrict__ ctl, uint32_t *__restrict__ total, uint32_t *__restrict__ flag, uint32_t *__restrict__ tile_next,
+                                 uint32_t *host_total, uint32_t *host_flag)
 {
     if (threadIdx.x < 8) tile_next[16 * threadIdx.x] = 0u;
     if (threadIdx.x == 0) {
         const uint32_t f = ctl[1];
+        /* the host's copies (the sketch's slot): the true total, whatever the device's copy says below, and the flag */
+        if (host_total) { ntl_host_store32(host_total, *total); ntl_host_store32(host_flag, f); }
         *flag = f;
         if (f) *total = 0xFFFFFFFFu;
     }
+}
+
+/* the lookup's hit count into the sketch's slot, for a sketch that no map kernel has taken it from (sketch_finalize) */
+__global__ void sketch_nfound_kernel(const unsigned long long *nfound, unsigned long long *host_nfound)
+{
+    if (threadIdx.x == 0) ntl_host_store64(host_nfound, *nfound);
 }
 
 /* offsets of the per-sequence lists: the rank of the first minimizer of a sequence's first strip (a sequence without strips: of the
