@@ -73,47 +73,6 @@ def library_is_current(extra_flags=()):
 last_action = None  # "rebuilt" | "reused": what the last build_hip() of this process did
 
 
-def _sha(paths, extra=""):
-    h = hashlib.sha256(extra.encode())
-    for p in paths:
-        h.update(os.path.basename(p).encode() + b"\0")
-        with open(p, "rb") as fh:
-            h.update(fh.read())
-    return h.hexdigest()
-
-
-def _flags(extra_flags=()):
-    # NTL_EXTRA_HIPCC_FLAGS: tools only (e.g. -DNTL_SKETCH_ABLATION for tools/gpu_ablate.sh).  The include path is written relative to
-    # the signature: the same sources under another root are the same build
-    return ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-result", *extra_flags,
-            *os.environ.get("NTL_EXTRA_HIPCC_FLAGS", "").split()]
-
-
-def _unit_deps(unit):
-    return [os.path.join(CSRC, unit), HEADER] + [os.path.join(CSRC, h) for h in UNITS[unit] if os.path.exists(os.path.join(CSRC, h))]
-
-
-def source_signature(extra_flags=()):
-    """sha256 over every source of the library and the compiler flags: what `libntlink_hip.so.sig` must hold for the library to be current."""
-    flags = " ".join(_flags(extra_flags))
-    return _sha(sorted({d for u in UNITS for d in _unit_deps(u)}), flags)
-
-
-def _read(path):
-    try:
-        with open(path) as fh:
-            return fh.read().strip()
-    except OSError:
-        return None
-
-
-def library_is_current(extra_flags=()):
-    return os.path.exists(OUT) and _read(OUT + ".sig") == source_signature(extra_flags)
-
-
-last_action = None  # "rebuilt" | "reused": what the last build_hip() of this process did
-
-
 def build_hip(force=False, extra_flags=()):
     """Serialised across processes (several test workers may ask for the library at once): a file lock around the build."""
     import fcntl

@@ -45,12 +45,10 @@
  * batch i's latency-bound kernels; hipEvents carry the two real dependencies (window stage -> emit of the same batch; emit ->
  * the next user of the bitmask it read and cleared).  No call of the hot path waits on the host: sizes stay on the device,
  * result handles are completed lazily (sketch_finalize / mapres_finalize) when a count or a record is asked for.
+ * A third stream for a sketch's preparation (the per-sequence tables, the strip scan, the strip table) was measured twice and
+ * removed: the step got longer (profiles/HISTORY.md, profiles/r04_prep_stream.jsonl); those kernels run on the window stream.
  */
-/* SID_P (round 4, an experiment behind NTL_PREP_STREAM=1): a third stream that only runs a sketch's PREPARATION -- the per-sequence
- * tables, the scan of the strip counts, the strip table: small dependent kernels that need nothing but the batch and sit on the window
- * stream's critical path (C3: 2.5 of 71 ms per step).  On a stream of their own they run while the previous window kernel still does
- * -- and the step gets LONGER (ntl_ctx_create); by default SID_P is the window stream. */
-enum { SID_MAIN = 0, SID_W = 1, SID_P = 2, NTL_NSID = 3 };
+enum { SID_MAIN = 0, SID_W = 1, NTL_NSID = 2 };
 
 struct ProfEntry {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> spans;
@@ -61,7 +59,7 @@ struct ProfEntry {
 /* a cached device block that was used on both streams: whoever takes it waits for the events of the streams it is not on */
 struct XBlock {
     void *p = nullptr;
-    hipEvent_t ev[NTL_NSID] = {nullptr, nullptr, nullptr}; /* nullptr: not used on that stream */
+    hipEvent_t ev[NTL_NSID] = {}; /* nullptr: not used on that stream */
 };
 
 /* a zero-filled minimizer bitmask whose last reader (emit_kernel) cleared what the window stage had set */
@@ -90,12 +88,10 @@ struct ntl_ctx {
     hipStream_t stream = nullptr;  /* MAIN */
     hipStream_t wstream = nullptr; /* window stage; == stream when the pipeline is off */
     hipStream_t wstream_own = nullptr; /* the second stream itself (ntl_ctx_set_pipeline switches wstream between it and MAIN) */
-    hipStream_t pstream = nullptr, pstream_own = nullptr; /* a sketch's preparation (SID_P); == stream when the pipeline is off */
     bool pipelined = false;
     std::string err;
     std::string async_err;         /* first failure of work whose handle was already gone: reported by ntl_ctx_sync */
     std::string devname;
-    int skw_budget = 0;            /* two streams: chunks of strips a window wavefront takes before it ends (0: resident wavefronts; tuning) */
     int n_cu = 1;                  /* compute units of the device: the grid of a kernel whose wavefronts stay resident */
     std::map<const void *, int> occ; /* kernel -> workgroups one CU holds (hipOccupancyMaxActiveBlocksPerMultiprocessor, asked once) */
     bool prof = false;
@@ -119,8 +115,8 @@ struct ntl_ctx {
     std::multimap<size_t, void *> slab_free;   /* dropped slab blocks by size */
     std::unordered_map<void *, size_t> slab_size; /* every slab block's TRUE size (a reused block may be up to 25 % larger than what was asked for; round 6) */
     /* slab blocks that were given back while work on them may still be queued: they join slab_free when the events recorded behind that
-       work have passed (polled by dev_alloc) -- no stream is waited for (round 6, ADVICE r5: dev_free used to synchronise all three) */
-    struct Limbo { void *p; size_t bytes; hipEvent_t ev[3]; };
+       work have passed (polled by dev_alloc) -- no stream is waited for (round 6, ADVICE r5: dev_free used to synchronise them) */
+    struct Limbo { void *p; size_t bytes; hipEvent_t ev[NTL_NSID]; };
     std::deque<Limbo> slab_limbo;
     char *slab_cur = nullptr, *slab_end = nullptr;
     std::mutex slab_mu; /* (dev_free may be asked about another context's block: index_unref) */
@@ -134,13 +130,8 @@ struct ntl_ctx {
     std::deque<Zombie> zombies;
     hipEvent_t throttle[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint64_t n_enqueued = 0;            /* sketches queued so far: the host runs at most 8 of them ahead of the device */
-    hipStream_t s(int sid) const { return sid == SID_W ? wstream : (sid == SID_P ? pstream : stream); }
-    int sid(int want) const
-    {
-        if (!pipelined) return SID_MAIN;
-        if (want == SID_P && pstream == wstream) return SID_W; /* no stream of its own: the preparation is window-stage work */
-        return want;
-    }
+    hipStream_t s(int sid) const { return sid == SID_W ? wstream : stream; }
+    int sid(int want) const { return pipelined ? want : SID_MAIN; }
 };
 #define NTL_NSLOTS 512u
 
@@ -331,37 +322,39 @@ static ntl_ctx::Slab *slab_of(ntl_ctx *c, const void *p)
     return nullptr;
 }
 
-/* Gives a block of dev_alloc (of `bytes`, as asked for there) back.  A single block: hipFree, which waits for the device.  A slab
-   block: the same wait -- whatever is still queued on the block has run -- and then onto the slabs' free list. */
 static void slab_limbo_poll(ntl_ctx *c, bool wait); /* (slab_mu held) */
 
+/* Gives a block of dev_alloc (of `bytes`, as asked for there) back.  A single block: hipFree.  A slab block is not waited for: an
+   event is recorded behind each of the context's streams and the block goes into limbo; it joins the slabs' free list when the
+   events have passed (slab_limbo_poll).  slab_mu is held around the slabs' bookkeeping only, never across a call that may wait. */
 static void dev_free(ntl_ctx *c, void *p, size_t bytes)
 {
     if (!p) return;
-    (void)bytes;
-    std::lock_guard<std::mutex> g(c->slab_mu);
-    ntl_ctx::Slab *sl = slab_of(c, p);
-    if (!sl) { (void)hipFree(p); return; }
+    ntl_ctx::Limbo L = {};
+    {
+        std::lock_guard<std::mutex> g(c->slab_mu);
+        if (slab_of(c, p)) {
+            L.p = p;
+            auto ts = c->slab_size.find(p);
+            L.bytes = ts != c->slab_size.end() ? ts->second : ((bytes + 255) & ~(size_t)255);
+        }
+    }
+    if (!L.p) { (void)hipFree(p); return; }
     /* what is still queued on the block: an event behind each of the context's streams (made here, not taken from the context's event
        list: this may be another context's thread, index_unref); no event to be had: the slow, safe way */
-    ntl_ctx::Limbo L;
-    L.p = p;
-    auto ts = c->slab_size.find(p);
-    L.bytes = ts != c->slab_size.end() ? ts->second : ((bytes + 255) & ~(size_t)255);
-    hipStream_t st[3] = {c->stream, c->wstream != c->stream ? c->wstream : nullptr,
-                         c->pstream != c->stream && c->pstream != c->wstream ? c->pstream : nullptr};
+    hipStream_t st[NTL_NSID] = {c->stream, c->wstream != c->stream ? c->wstream : nullptr};
     bool ok = true;
-    for (int i = 0; i < 3; i++) {
-        L.ev[i] = nullptr;
-        if (i && !st[i]) continue;
-        if (hipEventCreateWithFlags(&L.ev[i], hipEventDisableTiming) != hipSuccess || hipEventRecord(L.ev[i], st[i]) != hipSuccess) { ok = false; break; }
-    }
+    for (int i = 0; i < NTL_NSID && ok; i++)
+        if (st[i]) ok = hipEventCreateWithFlags(&L.ev[i], hipEventDisableTiming) == hipSuccess && hipEventRecord(L.ev[i], st[i]) == hipSuccess;
     if (!ok) {
         (void)hipGetLastError();
-        for (int i = 0; i < 3; i++) if (L.ev[i]) { (void)hipEventDestroy(L.ev[i]); L.ev[i] = nullptr; }
+        for (int i = 0; i < NTL_NSID; i++) if (L.ev[i]) { (void)hipEventDestroy(L.ev[i]); L.ev[i] = nullptr; }
         (void)sync_both(c);
     }
-    if (sl->live) sl->live--;
+    /* (the slab is looked up again: dev_alloc may have added one meanwhile; this block's own slab stays, it still counts as live) */
+    std::lock_guard<std::mutex> g(c->slab_mu);
+    ntl_ctx::Slab *sl = slab_of(c, p);
+    if (sl && sl->live) sl->live--;
     c->slab_limbo.push_back(L);
     slab_limbo_poll(c, false);
 }
@@ -371,14 +364,14 @@ static void slab_limbo_poll(ntl_ctx *c, bool wait)
 {
     for (auto it = c->slab_limbo.begin(); it != c->slab_limbo.end();) {
         bool done = true;
-        for (int i = 0; i < 3 && done; i++)
+        for (int i = 0; i < NTL_NSID && done; i++)
             if (it->ev[i]) {
                 hipError_t q = wait ? hipEventSynchronize(it->ev[i]) : hipEventQuery(it->ev[i]);
                 if (q == hipErrorNotReady) done = false;
             }
         if (!done) { ++it; continue; }
         (void)hipGetLastError();
-        for (int i = 0; i < 3; i++) if (it->ev[i]) (void)hipEventDestroy(it->ev[i]);
+        for (int i = 0; i < NTL_NSID; i++) if (it->ev[i]) (void)hipEventDestroy(it->ev[i]);
         c->slab_free.insert({it->bytes, it->p});
         it = c->slab_limbo.erase(it);
     }
@@ -528,8 +521,7 @@ struct DevBuf {
             return NTL_OK;
         }
         /* A block that was used on several streams: one whose work on the OTHER streams has run by now is taken as it is; else a
-           new block is made rather than this stream made to wait (the preparation of sub-batch i+1 would wait for the window
-           kernel of sub-batch i, which is what the third stream is there to avoid; two or three blocks per size then go round);
+           new block is made rather than this stream made to wait (two or three blocks per size then go round);
            only when no memory is to be had does the taker wait. */
         auto first = c->xpool.lower_bound(want), pick = c->xpool.end();
         for (auto xt = first; xt != c->xpool.end() && xt->first <= most; ++xt) {
@@ -562,7 +554,8 @@ struct DevBuf {
     void release()
     {
         if (p && c) {
-            if (used == 1u || used == 2u || used == 4u) c->pool[used >> 1].insert({bytes, p});
+            const bool on_main = used & (1u << SID_MAIN), on_w = used & (1u << SID_W);
+            if (on_main != on_w) c->pool[on_w ? SID_W : SID_MAIN].insert({bytes, p}); /* one stream: its own cache */
             else {
                 XBlock x;
                 x.p = p;
@@ -661,17 +654,6 @@ extern "C" int ntl_ctx_create(int device, ntl_ctx **out)
         if (e2 != hipSuccess) { c->wstream = c->stream; c->pipelined = false; }
         else c->wstream_own = c->wstream;
     }
-    c->pstream = c->stream;
-    /* NTL_PREP_STREAM=1 only: measured and NOT kept as the default (profiles/r04_prep_stream.jsonl: C3 75.5-76.0 ms per step against
-       72.6-73.1, C5 278-283 against 259-266) -- with the window kernels back to back the lookup kernel of the other stream never
-       gets the whole device for the 0.1 ms the preparation takes, and loses more (42 -> 57 ms per step) than the window stage gains */
-    if (c->pipelined && getenv("NTL_PREP_STREAM") && atoi(getenv("NTL_PREP_STREAM")) != 0) {
-        /* the preparation's few small kernels are wanted early: the highest priority */
-        hipError_t e3 = prio ? hipStreamCreateWithPriority(&c->pstream_own, hipStreamNonBlocking, greatest)
-                             : hipStreamCreateWithFlags(&c->pstream_own, hipStreamNonBlocking);
-        if (e3 != hipSuccess) c->pstream_own = nullptr;
-    }
-    c->pstream = c->pipelined ? (c->pstream_own ? c->pstream_own : c->wstream) : c->stream;
     {
         uint64_t g4[256][2];
         make_g4(g4);
@@ -730,7 +712,6 @@ static hipError_t sync_both(ntl_ctx *c)
 {
     hipError_t e = hipStreamSynchronize(c->stream);
     if (c->wstream != c->stream) { const hipError_t e2 = hipStreamSynchronize(c->wstream); if (e == hipSuccess) e = e2; }
-    if (c->pstream != c->stream && c->pstream != c->wstream) { const hipError_t e3 = hipStreamSynchronize(c->pstream); if (e == hipSuccess) e = e3; }
     return e;
 }
 
@@ -760,7 +741,6 @@ extern "C" void ntl_ctx_destroy(ntl_ctx *c)
     for (auto &e : c->throttle) sev_put(c, e);
     for (auto e : c->sev_free) (void)hipEventDestroy(e);
     if (c->wstream_own) (void)hipStreamDestroy(c->wstream_own);
-    if (c->pstream_own) (void)hipStreamDestroy(c->pstream_own);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -780,15 +760,12 @@ extern "C" int ntl_ctx_set_pipeline(ntl_ctx *c, int on)
     if (on && !c->wstream_own) return fail(c, NTL_EINVAL, "this context was created without a window stream (NTL_PIPELINE=0)");
     c->pipelined = on != 0;
     c->wstream = on ? c->wstream_own : c->stream;
-    c->pstream = on ? (c->pstream_own ? c->pstream_own : c->wstream) : c->stream;
     /* Everything queued has run (both streams were drained above), so every cached block is free on either stream: they all
        move to MAIN's cache.  Switching off, sid() maps every request to MAIN and the window-stage blocks would otherwise lie
        stranded in pool[SID_W] (counted, never handed out: the next step allocated its temporaries anew); switching on, the
        window stage's first requests miss its own cache once and are served from then on. */
-    for (int i = 1; i < NTL_NSID; i++) {
-        for (auto &kv : c->pool[i]) c->pool[SID_MAIN].insert(kv);
-        c->pool[i].clear();
-    }
+    for (auto &kv : c->pool[SID_W]) c->pool[SID_MAIN].insert(kv);
+    c->pool[SID_W].clear();
     for (auto &kv : c->xpool) {
         c->pool[SID_MAIN].insert({kv.first, kv.second.p});
         for (int o = 0; o < NTL_NSID; o++) sev_put(c, kv.second.ev[o]);
@@ -896,7 +873,7 @@ struct ntl_batch {
     /* a batch whose creating call returned without waiting (the synthetic ones): recorded on MAIN behind its last kernel;
        the window stream waits for it once */
     hipEvent_t ready = nullptr;
-    mutable bool w_waited = false, p_waited = false;
+    mutable bool w_waited = false;
 };
 
 static void batch_unref(const ntl_batch *cb)
@@ -915,10 +892,6 @@ static void batch_on_wstream(ntl_ctx *c, const ntl_batch *b)
     if (!c->pipelined) return;
     if (b->ready && !b->w_waited) { (void)hipStreamWaitEvent(c->wstream, b->ready, 0); b->w_waited = true; }
     b->packed.touch(SID_W); b->seq_base.touch(SID_W); b->seq_run_first.touch(SID_W); b->run_start.touch(SID_W); b->run_len.touch(SID_W);
-    if (c->pstream != c->wstream) { /* the preparation reads the sequence and run tables on its own stream */
-        if (b->ready && !b->p_waited) { (void)hipStreamWaitEvent(c->pstream, b->ready, 0); b->p_waited = true; }
-        b->seq_base.touch(SID_P); b->seq_run_first.touch(SID_P); b->run_start.touch(SID_P); b->run_len.touch(SID_P);
-    }
 }
 
 /* Host arrays in, device layout out: the bases travel as they are (one byte each) and are packed and
@@ -1547,7 +1520,7 @@ static void launch_fast_r0(ntl_ctx *c, const Sketch2Args &B, unsigned strips)
                        the other stream's kernels leave free (those have the higher stream priority and a bounded number of
                        resident workgroups: sketch_enqueue, emit) -- and the whole CU while that stream has nothing to run. */
                     Sketch2Args Bq = B;
-                    int budget = c->pipelined ? c->skw_budget : 0;
+                    int budget = 0; /* (0: resident wavefronts; tuning, tools/share_sweep.py) */
                     if (const char *e = getenv("NTL_SKW_BUDGET")) budget = atoi(e);
                     if (budget >= 2) {
                         const unsigned per_xcd_chunks = (((strips + 7u) >> 3) + SKW_CHUNK - 1u) / SKW_CHUNK;
@@ -1706,8 +1679,8 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     int C, nt, rc;
     if ((rc = sketch_geometry(c, k, w, G, C, nt))) return rc;
     const uint64_t nseq = b->nseq;
-    const int wsid = c->sid(SID_W), psid = c->sid(SID_P);
-    hipStream_t ws = c->s(wsid), ms = c->stream, ps = c->s(psid);
+    const int wsid = c->sid(SID_W);
+    hipStream_t ws = c->s(wsid), ms = c->stream;
     /* the host runs at most 8 sketches ahead of the device */
     {
         hipEvent_t &t = c->throttle[c->n_enqueued & 7u];
@@ -1717,14 +1690,14 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     DevBuf run_n, run_ord, seq_M, nstrips, strip_first, tile, redo, strip_tab;
     /* nstrips / strip_first hold nseq+1 entries: the scan leaves the total behind the last one */
     const uint64_t nmask = (b->total_gpos + 31) / 32 + 1;
-    /* the preparation's arrays: made on its stream (psid), and those the window stage reads marked as used there too */
-    if ((rc = run_n.alloc(c, (b->nruns + 1) * 4, psid)) || (rc = run_ord.alloc(c, (b->nruns + 1) * 4, psid)) ||
-        (rc = seq_M.alloc(c, (nseq + 1) * 4, psid)) || (rc = nstrips.alloc(c, (nseq + 1) * 4, psid)) ||
-        (rc = strip_first.alloc(c, (nseq + 2) * 4, psid)) || (rc = s->mx_off.alloc(c, (nseq + 1) * 4)) ||
-        (rc = s->sums.alloc(c, sizeof(SketchSums), psid))) {
+    /* the preparation's arrays: made on the window stream, where its kernels run in front of the window kernels */
+    if ((rc = run_n.alloc(c, (b->nruns + 1) * 4, wsid)) || (rc = run_ord.alloc(c, (b->nruns + 1) * 4, wsid)) ||
+        (rc = seq_M.alloc(c, (nseq + 1) * 4, wsid)) || (rc = nstrips.alloc(c, (nseq + 1) * 4, wsid)) ||
+        (rc = strip_first.alloc(c, (nseq + 2) * 4, wsid)) || (rc = s->mx_off.alloc(c, (nseq + 1) * 4)) ||
+        (rc = s->sums.alloc(c, sizeof(SketchSums), wsid))) {
         return rc;
     }
-    s->sums.touch(SID_MAIN); /* zeroed by strip_table_kernel on the preparation's stream, added to and read on MAIN */
+    s->sums.touch(SID_MAIN); /* zeroed by strip_table_kernel on the window stream, added to and read on MAIN */
     batch_on_wstream(c, b);
     SeqTables T;
     T.packed = b->packed.as<uint32_t>(); T.seq_base = b->seq_base.as<uint64_t>();
@@ -1784,7 +1757,6 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
                 (rc = loff.alloc(c, (ub_strips + 2) * 4))) return rc;
             lcnt.touch(SID_MAIN); lent.touch(SID_MAIN);
             Ls.cnt = lcnt.as<uint32_t>(); Ls.ent = lent.as<uint32_t>(); Ls.ctl = Ls.cnt + ub_strips + 2;
-            lcnt.touch(SID_P); /* (zeroed by strip_table_kernel, on the preparation's stream) */
         }
     }
     /* the fast pass's counters and lists: [0] strips for the exact pass, [1] strips the threshold pass gave up, then the eight chunk
@@ -1795,7 +1767,6 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     const uint64_t redo_head = 16 + 8 * 16; /* words in front of the lists */
     if (fast && ub_strips) {
         if ((rc = redo.alloc(c, (redo_head + 2 * ub_strips + 4) * 4, wsid))) return rc;
-        redo.touch(SID_P);
         Z.head = redo.as<uint32_t>(); Z.nhead = (uint32_t)redo_head;
         Z.cnt = Ls.cnt; Z.ncnt = Ls.cnt ? (uint32_t)(ub_strips + 4) : 0u;
     }
@@ -1805,37 +1776,29 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
         ntl_ctx *c; CleanMask *m;
         ~MaskGuard() { if (m->p) { dev_free(c, m->p, m->bytes); m->p = nullptr; } }
     } mask_guard{c, &mask};
-    if ((rc = strip_tab.alloc(c, (ub_strips + 1) * sizeof(StripInfo), psid))) return rc;
+    if ((rc = strip_tab.alloc(c, (ub_strips + 1) * sizeof(StripInfo), wsid))) return rc;
     DevBuf strip_lite;
-    if ((rc = strip_lite.alloc(c, (ub_strips + 1) * sizeof(StripLite), psid))) return rc;
-    run_n.touch(SID_W); run_ord.touch(SID_W); seq_M.touch(SID_W); strip_tab.touch(SID_W); strip_lite.touch(SID_W);
+    if ((rc = strip_lite.alloc(c, (ub_strips + 1) * sizeof(StripLite), wsid))) return rc;
     SketchSums *dsums = s->sums.as<SketchSums>();
-    /* the device sums are zeroed by strip_table_kernel (StripZero); every kernel that writes them runs on MAIN behind the window
-       stage, which waits for the preparation (the events below; one stream when the pipeline is off).  No sequence, no kernel: a fill */
+    /* the device sums are zeroed by strip_table_kernel (StripZero), in front of the window kernels on their stream; every kernel that
+       writes them runs on MAIN behind the window stage (the event below; one stream when the pipeline is off).  No sequence, no kernel: a fill */
     Z.sums = (uint32_t *)dsums; Z.nsums = (uint32_t)(sizeof(SketchSums) / 4);
     if (!nseq) HIPCHK(c, hipMemsetAsync(dsums, 0, sizeof(SketchSums), ms));
     {
-        ProfSpan sp(c, "sketch_meta", psid);
+        ProfSpan sp(c, "sketch_meta", wsid);
         if (nseq) {
             KTables K;
             K.run_n = run_n.as<uint32_t>(); K.run_ord = run_ord.as<uint32_t>();
             K.seq_M = seq_M.as<uint32_t>(); K.seq_nstrips = nstrips.as<uint32_t>();
-            hipLaunchKernelGGL(seq_meta_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, ps, T, K, k, w, G.NWO);
+            hipLaunchKernelGGL(seq_meta_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, ws, T, K, k, w, G.NWO);
             HIPCHK(c, hipGetLastError());
-            if ((rc = device_scan(c, nstrips.as<uint32_t>(), strip_first.as<uint32_t>(), nseq, nullptr, 1, nullptr, psid))) return rc;
-            hipLaunchKernelGGL(strip_table_kernel, dim3((unsigned)((ub_strips + 255) / 256 + 1)), dim3(256), 0, ps, T,
+            if ((rc = device_scan(c, nstrips.as<uint32_t>(), strip_first.as<uint32_t>(), nseq, nullptr, 1, nullptr, wsid))) return rc;
+            hipLaunchKernelGGL(strip_table_kernel, dim3((unsigned)((ub_strips + 255) / 256 + 1)), dim3(256), 0, ws, T,
                                (const uint32_t *)run_n.as<uint32_t>(), (const uint32_t *)run_ord.as<uint32_t>(),
                                (const uint32_t *)seq_M.as<uint32_t>(), (const uint32_t *)strip_first.as<uint32_t>(), G.NWO,
                                C * nt, strip_tab.as<StripInfo>(), (uint32_t)ub_strips + 1u, strip_lite.as<StripLite>(), Z);
             HIPCHK(c, hipGetLastError());
         }
-    }
-    if (ps != ws && nseq) { /* preparation -> window stage */
-        hipEvent_t e = sev_get(c);
-        if (!e) return fail(c, NTL_EDEVICE, "hipEventCreate failed");
-        HIPCHK(c, hipEventRecord(e, ps));
-        HIPCHK(c, hipStreamWaitEvent(ws, e, 0));
-        sev_put(c, e); /* the wait holds what it needs; the handle may be recorded again */
     }
     if (ub_strips) {
         SketchArgs A;

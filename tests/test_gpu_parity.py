@@ -464,11 +464,10 @@ def test_async_order_and_unseen_results(dev, monkeypatch):
     dev.sync()
 
 
-def test_preparation_on_a_stream_of_its_own(monkeypatch):
-    """NTL_PREP_STREAM=1 (an experiment that is not the default): a sketch's per-sequence tables and strip table
-    are made on a third stream while the previous window kernel still runs; their arrays go round in the cross-stream block cache
-    (a block whose other streams are still busy is not waited for, another one is made).  Same records, same mappings."""
-    monkeypatch.setenv("NTL_PREP_STREAM", "1")
+def test_first_sketches_of_a_fresh_context():
+    """A fresh context's first sketches: both block caches start cold (every array is a new block), and the arrays used on both
+    streams go round in the cross-stream block cache (a block whose other stream is still busy is not waited for, another one is
+    made).  Same records, same mappings."""
     chroms, cbuf, coff, names, _ = synth.make_assembly(3, 1, 10, 200_000)
     rbuf, roff, _ = synth.make_reads(4, chroms, 5_000_000, 12_000, 0.02, 0.015, 0.015, lognormal_sigma=0.4)
     contigs = [cbuf[int(coff[i]):int(coff[i + 1])].tobytes() for i in range(len(coff) - 1)]

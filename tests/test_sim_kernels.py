@@ -395,12 +395,11 @@ def test_sim_handles_outlive_their_inputs(monkeypatch):
         d.close()
 
 
-def test_sim_preparation_on_a_stream_of_its_own(monkeypatch):
-    """NTL_PREP_STREAM=1 under the mock: the third stream's code path (three block caches, blocks used on several streams going
-    round) -- the mock runs streams in order, so this checks the bookkeeping, the GPU test the concurrency."""
+def test_sim_first_sketches_of_a_fresh_context():
+    """A fresh context's first sketches under the mock: both block caches start cold, and the blocks used on both streams go round
+    the cross-stream cache -- the mock runs streams in order, so this checks the bookkeeping, the GPU test the concurrency."""
     contigs = pc.fixture_seqs("scaffolds_4.fa")
     reads = pc.fixture_seqs("long_reads_4_top5.fa")
-    monkeypatch.setenv("NTL_PREP_STREAM", "1")
     d = simlib.device()
     try:
         assert pc.check_async_order(d, contigs, reads, 40, 100, z=1000) > 0
