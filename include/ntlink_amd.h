@@ -48,8 +48,8 @@
  * lane, lanes per strip of the sketch kernel), NTL_SKETCH_FAST=0 (exact 64-bit window pass only), NTL_SKETCH_FORCE_REDO=1
  * (every strip takes the 32-bit passes and the exact pass), NTL_SKETCH_THRESH (0: the block-minima window pass for every
  * window instead of the threshold pass for 71 <= w <= 255; x: x candidates per window instead of 10), NTL_SKETCH_THRESH_DIRECT=1
- * (the threshold pass without staged keys for the large windows too), NTL_SKETCH_LANES=1 and NTL_EMIT_U=2 (kernel variants kept
- * for the record), NTL_PIPELINE=0 (one stream per context; default: a second stream for
+ * (the threshold pass without staged keys for the large windows too), NTL_EMIT_U=2 (a kernel variant kept for the record; the
+ * NTL_SKETCH_LANES experiment's code has left the tree, profiles/HISTORY.md 4.12 is its record), NTL_PIPELINE=0 (one stream per context; default: a second stream for
  * the window stage), NTL_PIPELINE_PRIO (0 no stream priorities, 1 = default: MAIN above the window stream, 2 the reverse),
  * NTL_SKETCH_CAP_GUESS (records a sketch's arrays hold before its count is known; tests force the second round with it).
  */

@@ -26,6 +26,7 @@
 #include "sketch_kernels.h"
 #include "sketch2_kernels.h"
 #include "sketch_small_kernels.h"
+#include "window_plan.h"
 #include "map_kernels.h"
 #include "pack_kernels.h"
 #include "synth_kernels.h"
@@ -1406,17 +1407,23 @@ static void make_g8(std::vector<uint64_t> &g8)
     }
 }
 
+/* calls f(std::integral_constant<int, v>()) for the v in [LO, HI) that `value` equals: a run-time value becomes a template argument */
+template <int LO, int HI, typename F>
+static void with_constant(int value, F &&f)
+{
+    if constexpr (LO < HI) {
+        if (value == LO) f(std::integral_constant<int, LO>());
+        else with_constant<LO + 1, HI>(value, f);
+    }
+}
+
 /* exact 64-bit pass: over all strips (multi-run strips when `multi`), or -- redo != NULL -- over the strips the fast pass flagged */
 template <int C, int NT, int R0>
 static void launch_mask_r0(ntl_ctx *c, const SketchArgs &A, unsigned strips, bool single, bool multi)
 {
-    if (R0 < 0 || A.G.r0 == R0) {
-        const unsigned grid = A.redo_list ? 2048u : ((strips + 7u) & ~7u);
-        if (single) hipLaunchKernelGGL((sketch_mask_kernel<C, NT, false, R0>), dim3(grid), dim3(NT), 0, c->wstream, A);
-        if (multi) hipLaunchKernelGGL((sketch_mask_kernel<C, NT, true, R0>), dim3((strips + 7u) & ~7u), dim3(NT), 0, c->wstream, A);
-        return;
-    }
-    if constexpr (R0 >= 0 && R0 + 1 < C) launch_mask_r0<C, NT, R0 + 1>(c, A, strips, single, multi);
+    const unsigned grid = A.redo_list ? 2048u : ((strips + 7u) & ~7u);
+    if (single) hipLaunchKernelGGL((sketch_mask_kernel<C, NT, false, R0>), dim3(grid), dim3(NT), 0, c->wstream, A);
+    if (multi) hipLaunchKernelGGL((sketch_mask_kernel<C, NT, true, R0>), dim3((strips + 7u) & ~7u), dim3(NT), 0, c->wstream, A);
 }
 
 template <int C>
@@ -1426,7 +1433,7 @@ static void launch_mask(ntl_ctx *c, const SketchArgs &A, unsigned strips, bool s
        window pass took over the common case); 4 and 1 k-mers per lane (w < 16): R0 as a template parameter */
     if (C == 16 && nt == 128) launch_mask_r0<C, 128, -1>(c, A, strips, single, multi);
     else if (C == 16) launch_mask_r0<C, SK_NT, -1>(c, A, strips, single, multi);
-    else launch_mask_r0<C, SK_NT, 0>(c, A, strips, single, multi);
+    else with_constant<0, C>(A.G.r0, [&](auto r0) { launch_mask_r0<C, SK_NT, decltype(r0)::value>(c, A, strips, single, multi); });
 }
 
 /* workgroups of `threads` lanes of a kernel that one CU holds at once */
@@ -1458,113 +1465,12 @@ static void ctx_prime(ntl_ctx *c)
         DevBuf first;
         (void)first.alloc(c, 1 << 20);
     }
-    c->occ[(const void *)sketch_wave_kernel<8, 11, 4>] = occupancy_blocks(sketch_wave_kernel<8, 11, 4>, 512);
-    c->occ[(const void *)sketch_wave_kernel<8, 15, 6>] = occupancy_blocks(sketch_wave_kernel<8, 15, 6>, 512);
-    c->occ[(const void *)sketch_wave_kernel<8, 19, 8>] = occupancy_blocks(sketch_wave_kernel<8, 19, 8>, 512);
-    c->occ[(const void *)sketch_wave_kernel<4, 19, 8>] = occupancy_blocks(sketch_wave_kernel<4, 19, 8>, 256);
+    for (int s = 0; s < WS_DEFAULTS; s++)
+        with_wave_kernel((WaveShape)s, [&](auto kern, unsigned threads) { c->occ[(const void *)kern] = occupancy_blocks(kern, (int)threads); });
     c->err.clear();
 #else
     (void)c;
 #endif
-}
-
-/* does the window pass of this sketch run as sketch_wave_kernel (one wavefront per strip)?  Where a lane's first k-mer lies in its own
-   64 bases and a strip's candidates fit its list; NTL_SKETCH_WAVE=0: the workgroup-per-strip form (A/B, tests).  Read per call: the
-   tests switch it inside one process. */
-static int wave_form(const Sketch2Args &B, int nt)
-{
-    const char *we = getenv("NTL_SKETCH_WAVE");
-    const int wave = we ? atoi(we) : 1;
-    const double per_strip = 4096.0 * (double)B.thresh / 4294967296.0; /* candidates a strip is expected to hold */
-    /* (a + 2 <= 16, w <= 255, is the workgroup-per-strip passes' limit, not this kernel's: a window only enters its scans as a distance.
-       Round 6: up to the block-minima pass's w <= 1135, which decides the strips it gives up) */
-    if (nt == 256 && B.thresh && B.A.G.a + 2 <= SK2_PAD && (B.dbg & ~24) == 0 && wave && B.A.G.k <= 64 && per_strip <= 440.0) return wave;
-    return 0;
-}
-
-/* fast 32-bit pass over the single-run strips (sketch2_kernels.h) */
-template <int NT, int R0>
-static void launch_fast_r0(ntl_ctx *c, const Sketch2Args &B, unsigned strips)
-{
-    if (B.A.G.r0 == R0) {
-        const dim3 grid((strips + 7u) & ~7u);
-        /* the 20-KB variants hold 128 searched windows per strip: about NWO / (w + 1) are expected (38 at w = 100) */
-        /* NTL_SKETCH_LANES=1: sketch_lanes_kernel, the variant that walks only the lanes whose minimum can change -- 30 % fewer
-           VALU instructions, but its single-wavefront phases halve the number of runnable wavefronts per SIMD and the launch
-           takes 5-6 % LONGER (profiles/r03*_lanes*): an experiment that is kept for the record, not the default */
-        const char *le = getenv("NTL_SKETCH_LANES"); /* read per call: the tests switch it inside one process */
-        const int lanes = le ? atoi(le) : 0;
-        /* the window pass on threshold-sparsified windows where the geometry allows it (B.thresh != 0) */
-        if (NT == 256 && B.thresh && (B.A.G.a + 2 <= 16 || wave_form(B, NT)) && (B.dbg & ~24) == 0) { /* (ablation bits 8 and 16 exist in this kernel too) */
-            /* one wavefront per strip, 64 k-mers per lane (sketch_wave_kernel, round 4) where a lane's first k-mer lies in its own
-               64 bases and a strip's candidates fit its list; NTL_SKETCH_WAVE=0: the workgroup-per-strip form (A/B, tests) */
-            const int wave = wave_form(B, NT);
-            const double per_strip = 4096.0 * (double)B.thresh / 4294967296.0; /* candidates a strip is expected to hold */
-            if (wave) {
-                /* resident wavefronts that walk over their strips: as many workgroups as the device holds at once (a multiple of 8:
-                   one share of the strips per XCD).  <wavefronts per workgroup, staging slots per lane, scan rounds>: the slots hold a
-                   lane's 64 p candidates + 4.5 sigma, the list (64 per round) a strip's 4096 p + 4 sigma; what does not fit is given up */
-                auto go = [&](auto kern, unsigned threads, unsigned beside = 16u) {
-                    int &per_cu = c->occ[(const void *)kern];
-                    if (!per_cu) per_cu = occupancy_blocks(kern, (int)threads);
-                    /* Beside the other stream's kernels (two streams: the lookup / map kernels of the previous batch) the resident wavefronts
-                       take HALF the CU's 32 slots: with more, those kernels' workgroups wait for slots that never come free before the
-                       launch ends, and the step is as long as on one stream (C3, profiles/r04_window_grid_sweep.json: 16 wavefronts per
-                       CU 77.6 ms per step, 24 89.5, 32 89.4; alone the launch takes 2.65 ms at 16 against 2.09 at 32). */
-                    int use = c->pipelined ? std::min(per_cu, (int)(beside / (threads / 64u))) : per_cu;
-                    if (const char *e = getenv("NTL_SKW_WGS_PER_CU")) use = std::max(1, std::min(per_cu, atoi(e))); /* tuning */
-                    unsigned wgs = (unsigned)std::max(1, use) * (unsigned)std::max(1, c->n_cu);
-                    wgs = std::min(wgs, (strips + threads / 64u - 1u) / (threads / 64u));
-                    wgs = (wgs + 7u) & ~7u;
-                    /* Two streams, NTL_SKW_BUDGET chunks per wavefront: short-lived workgroups, as many as it takes, that fill what
-                       the other stream's kernels leave free (those have the higher stream priority and a bounded number of
-                       resident workgroups: sketch_enqueue, emit) -- and the whole CU while that stream has nothing to run. */
-                    Sketch2Args Bq = B;
-                    int budget = 0; /* (0: resident wavefronts; tuning, tools/share_sweep.py) */
-                    if (const char *e = getenv("NTL_SKW_BUDGET")) budget = atoi(e);
-                    if (budget >= 2) {
-                        const unsigned per_xcd_chunks = (((strips + 7u) >> 3) + SKW_CHUNK - 1u) / SKW_CHUNK;
-                        const unsigned per_wg = (threads / 64u) * (unsigned)budget;
-                        wgs = 8u * ((per_xcd_chunks + per_wg - 1u) / per_wg);
-                        Bq.chunk_budget = (uint32_t)budget;
-                    }
-                    ProfSpan sp(c, "sketch_wave", SID_W); /* the window kernel alone (the span "sketch_mask" around this function also holds the block-minima pass) */
-                    hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), 0, c->wstream, Bq);
-                };
-                if (per_strip <= 175.0) { /* w >= 235 at ten candidates per window */
-                    /* (lists, round 5: the other stream's emit_list_kernel keeps to two resident workgroups per CU -- sketch_enqueue --
-                       and the window stage takes 24 of the 32 wavefront slots: C3 70.7 ms per step against 75.9 at 16 and 82.5 at
-                       32, profiles/r05_share_sweep_C3.jsonl) */
-                    const unsigned beside = B.A.Ls.cnt ? 24u : 16u;
-                    if (wave == 4) go(sketch_wave_kernel<4, 11, 4>, 256u, beside);
-                    else if (wave == 16) go(sketch_wave_kernel<16, 11, 4>, 1024u);
-                    else go(sketch_wave_kernel<8, 11, 4>, 512u, beside);
-                } else if (per_strip <= 300.0) { /* w >= 137 */
-                    go(sketch_wave_kernel<8, 15, 6>, 512u);
-                } else {                         /* w >= 94 */
-                    /* (dense sketches: the other stream's lookup and map kernels are the longer half of a step, and twelve resident
-                       wavefronts per CU beside them make the shortest step -- C5: 8 / 12 / 16 / 24: 304.6 / 288.5 / 315.1 / 318.7 ms) */
-                    if (wave == 4 || (c->pipelined && wave != 8)) go(sketch_wave_kernel<4, 19, 8>, 256u, 12u);
-                    else go(sketch_wave_kernel<8, 19, 8>, 512u);
-                }
-                if (B.A.G.a + 2 <= 16) hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0>), dim3(std::min(strips, 4096u)), dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
-                else hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0, true>), dim3(std::min(strips, 4096u)), dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
-                return;
-            }
-            const char *de = getenv("NTL_SKETCH_THRESH_DIRECT"); /* 1: the variant without staged keys for the large windows too (A/B) */
-            const int direct = de ? atoi(de) : 0;
-            if (direct || 4096.0 * (double)B.thresh / 4294967296.0 > 340.0) hipLaunchKernelGGL((sketch_thresh_kernel<256, true>), grid, dim3(256), 0, c->wstream, B);
-            else hipLaunchKernelGGL((sketch_thresh_kernel<256, false>), grid, dim3(256), 0, c->wstream, B);
-            /* what it gave up (a window without a candidate: 0.7 % of the strips): the block-minima pass over that list */
-            hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0>), dim3(std::min(strips, 4096u)), dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
-            return;
-        }
-        if (B.A.G.a + 2 <= 16 && B.A.G.w >= 64 && B.A.G.a >= 2 && lanes && B.dbg == 0) hipLaunchKernelGGL((sketch_lanes_kernel<NT, R0>), grid, dim3(NT), 0, c->wstream, B);
-        else if (B.A.G.a + 2 <= 16 && B.A.G.w >= 64) hipLaunchKernelGGL((sketch_fast_kernel<NT, R0, false>), grid, dim3(NT), 0, c->wstream, B);
-        else hipLaunchKernelGGL((sketch_fast_kernel<NT, R0, true>), grid, dim3(NT), 0, c->wstream, B);
-        return;
-    }
-    if constexpr (R0 + 1 < 16) launch_fast_r0<NT, R0 + 1>(c, B, strips);
 }
 
 /* a zero-filled bitmask of at least `bytes` for the window stage (stream sid): one that an earlier emit kernel cleared
@@ -1601,46 +1507,40 @@ static int mask_take(ntl_ctx *c, size_t bytes, int sid, CleanMask *out)
     return NTL_OK;
 }
 
-/* does the window pass of this window size run as sketch_small_kernel (2 <= w <= 15: the stages around `pair`)?  NTL_SKETCH_SMALL=0, or any
-   setting of the k-mers-per-lane knob: the round-1 forms with four / one k-mer per lane (A/B, tests).  Read per call. */
-static bool small_window_form(int w)
+static void launch_small(ntl_ctx *c, const SketchArgs &A, unsigned strips, bool multi)
 {
-    if (w < 2 || w > 15 || getenv("NTL_SKETCH_C")) return false;
-    const char *e = getenv("NTL_SKETCH_SMALL");
-    return !e || atoi(e) != 0;
-}
-
-template <int W>
-static void launch_small_w(ntl_ctx *c, const SketchArgs &A, unsigned strips, bool multi)
-{
-    if (A.G.w == W) {
+    with_constant<2, 16>(A.G.w, [&](auto w) {
+        constexpr int W = decltype(w)::value;
         const dim3 grid((strips + 7u) & ~7u);
         hipLaunchKernelGGL((sketch_small_kernel<W, false>), grid, dim3(256), 0, c->wstream, A);
         if (multi) hipLaunchKernelGGL((sketch_small_kernel<W, true>), grid, dim3(256), 0, c->wstream, A);
-        return;
-    }
-    if constexpr (W < 15) launch_small_w<W + 1>(c, A, strips, multi);
+    });
 }
 
 #ifndef NTL_EMIT_DENSE_CAP
 #define NTL_EMIT_DENSE_CAP 8192 /* emit_kernel's positions per round for the dense sketches of the small windows (sketch_kernels.h) */
 #endif
 
-/* geometry of the window pass for (k, w): k-mers per lane, lanes per strip */
-static int sketch_geometry(ntl_ctx *c, int k, int w, SketchGeom &G, int &C, int &nt)
+/* geometry of the window pass for (k, w): k-mers per lane, lanes per strip.  `small`: it runs as sketch_small_kernel (2 <= w <= 15: the
+   stages around `pair`); NTL_SKETCH_SMALL=0, or any setting of the k-mers-per-lane knob: the round-1 forms with four / one k-mer per
+   lane (A/B, tests).  The knobs are read per call: the tests switch them inside one process. */
+static int sketch_geometry(ntl_ctx *c, int k, int w, SketchGeom &G, int &C, int &nt, bool &small)
 {
     if (k < 1 || k > 4096 || w < 1) return fail(c, NTL_EINVAL, "k must be in 1..4096 and w >= 1");
     C = w >= 16 ? 16 : (w >= 4 ? 4 : 1);
     G.k = k; G.w = w;
-    if (small_window_form(w)) { /* sketch_small_kernel: 256 lanes x 16 k-mers, the minima of the 16 windows a lane starts in registers */
+    const char *ce = getenv("NTL_SKETCH_C"); /* tuning knob: k-mers per lane (16, 4, 1) */
+    small = w >= 2 && w <= 15 && !ce;
+    if (const char *e = small ? getenv("NTL_SKETCH_SMALL") : nullptr) small = atoi(e) != 0;
+    if (small) { /* sketch_small_kernel: 256 lanes x 16 k-mers, the minima of the 16 windows a lane starts in registers */
         C = 16; nt = SK_NT;
         G.a = 0; G.r0 = 0;
         G.LW = nt - 1;          /* the last lane only supplies the w - 1 elements behind the last window */
         G.NWO = G.LW * C - 1;
         return NTL_OK;
     }
-    if (const char *e = getenv("NTL_SKETCH_C")) { /* tuning knob: k-mers per lane (16, 4, 1) */
-        const int v = atoi(e);
+    if (ce) {
+        const int v = atoi(ce);
         if ((v == 16 || v == 4 || v == 1) && w >= v) C = v;
     }
     G.a = (w - C) / C; G.r0 = (w - C) % C;
@@ -1669,16 +1569,160 @@ static int sketch_geometry(ntl_ctx *c, int k, int w, SketchGeom &G, int &C, int 
     return NTL_OK;
 }
 
+/* The plan of one sketch (see WindowPlan): a pure function of (k, w), the batch's lengths, the number of streams, `no_lists` and the
+   knobs -- every knob that takes part is read here and nowhere else, per call: the tests switch them inside one process.  Nothing is
+   allocated or launched. */
+static int window_plan(ntl_ctx *c, const ntl_batch *b, int k, int w, bool no_lists, WindowPlan &P)
+{
+    memset(&P, 0, sizeof P);
+    bool small;
+    int rc;
+    if ((rc = sketch_geometry(c, k, w, P.G, P.C, P.nt, small))) return rc;
+    const SketchGeom &G = P.G;
+    for (uint64_t i = 0; i < b->nseq; i++) {
+        const uint64_t len = b->seq_len[i];
+        if (len + 2 > (uint64_t)k + (uint64_t)w) P.strips += (len - k - w + 2 + (uint64_t)G.NWO - 1) / (uint64_t)G.NWO;
+    }
+    if (P.strips >= 0x7FFFFFFFull) return fail(c, NTL_EINVAL, "batch too large: too many strips");
+    /* 32-bit fast pass + exact pass over what it flags; the exact pass alone for small windows / huge k */
+    bool fast = P.C == 16 && k <= 16 * SK2_QMAX && G.a + 2 <= SK2_PAD && !small;
+    if (const char *e = getenv("NTL_SKETCH_FAST")) fast = fast && atoi(e) != 0; /* 0: exact pass only (A/B, tests) */
+    P.pass = small ? WP_SMALL : WP_EXACT_ONLY;
+    if (!fast) return NTL_OK;
+    /* Threshold-sparsified windows where a strip's candidate list fits: keys below T = 2^32 * cpw / w are candidates,
+       cpw = 10 of them per window -- fewer and more strips have a window without one (they take the exact pass: 0.7 % at 10, 2 % at 9),
+       more and the list work grows (profiles/r03p_*).  NTL_SKETCH_THRESH=0: no threshold anywhere; = x: x candidates per window. */
+    const char *te = getenv("NTL_SKETCH_THRESH");
+    double cpw = te ? atof(te) : 10.0;
+    if (cpw == 1.0) cpw = 10.0;
+    if (cpw > 0 && P.nt != 128 && 4096.0 * cpw / w <= WP_FIT_THRESH) P.thresh = (uint32_t)std::min(4294967295.0, 4294967296.0 * cpw / w);
+    if (const char *e = getenv("NTL_SKETCH_ABLATE")) P.dbg = atoi(e); /* tools/sketch_bench.py only: results are wrong */
+    if (const char *e = getenv("NTL_SKETCH_FORCE_REDO")) P.force_redo = atoi(e); /* tests: every strip takes both passes */
+    P.expected_per_strip = 4096.0 * (double)P.thresh / 4294967296.0;
+    P.dense_windows = P.expected_per_strip > WP_FIT_15_6;
+    const bool sparse = P.thresh && (P.dbg & ~24) == 0; /* (ablation bits 8 and 16 exist in the threshold and wave kernels too) */
+    /* one wavefront per strip, 64 k-mers per lane (sketch_wave_kernel) where a lane's first k-mer lies in its own 64 bases and a strip's
+       candidates fit its list: a window only enters its scans as a distance, so it goes up to the block-minima pass's w <= 1135, which
+       decides the strips it gives up.  NTL_SKETCH_WAVE=0: the workgroup-per-strip forms; 4, 8, 16: wavefronts per workgroup (A/B, tests) */
+    const char *we = getenv("NTL_SKETCH_WAVE");
+    const int wave = we ? atoi(we) : 1;
+    if (sparse && wave && k <= 64 && P.expected_per_strip <= WP_FIT_WAVE) {
+        P.pass = WP_WAVE;
+        P.big = G.a + 2 > 16;
+    } else if (sparse && G.a + 2 <= 16) { /* the workgroup-per-strip passes' limit: w <= 255 */
+        P.pass = WP_THRESH;
+        const char *de = getenv("NTL_SKETCH_THRESH_DIRECT"); /* 1: the variant without staged keys for the large windows too (A/B) */
+        P.direct = (de && atoi(de)) || P.expected_per_strip > WP_FIT_STAGED;
+    } else {
+        P.pass = WP_BLOCK_MINIMA; /* the 20-KB variants hold 128 searched windows per strip: about NWO / (w + 1) are expected (38 at w = 100) */
+        P.big = G.a + 2 > 16 || w < 64;
+    }
+    if (P.pass != WP_WAVE) return NTL_OK;
+    /* Where the fast pass is sketch_wave_kernel (every window ntLink is run with) the passes write per-strip LISTS of minimizers
+       (sketch_kernels.h, StripLists) and emit_list_kernel reads those; everywhere else, a bitmask of one bit per base and emit_kernel.
+       NTL_SKETCH_LISTS=0: the bitmask everywhere (A/B, tests). */
+    P.lists = b->nseq && P.strips && !no_lists;
+    if (const char *e = getenv("NTL_SKETCH_LISTS")) P.lists = P.lists && atoi(e) != 0;
+    if (P.lists) {
+        /* a slot holds the expected 2 NWO / (w + 1) minimizers of a strip with room for their spread (what does not fit -- low-complexity
+           sequence -- lives in the pool behind the slots); the pool: 32 entries per strip, at least a million */
+        const double mean = 2.0 * (double)G.NWO / (double)(w + 1);
+        uint64_t slot = ((uint64_t)(mean * 1.25 + 24.0) + 15u) & ~(uint64_t)15u;
+        if (const char *e = getenv("NTL_LIST_SLOT")) slot = std::max<uint64_t>(1, (uint64_t)atoll(e)); /* tests: force strips into the pool */
+        uint64_t pool = std::max<uint64_t>((uint64_t)1 << 20, 32 * P.strips);
+        if (const char *e = getenv("NTL_LIST_POOL")) pool = (uint64_t)atoll(e);                      /* tests: make the pool run out */
+        if ((P.strips + 1) * slot + pool >= 0xFFFFFFF0ull) P.lists = false; /* (entries are addressed with 32 bits) */
+        else { P.slot = (uint32_t)slot; P.pool = (uint32_t)pool; }
+    }
+    /* Beside the other stream's kernels (two streams: the lookup / map kernels of the previous batch) the resident wavefronts take HALF the
+       CU's 32 slots: with more, those kernels' workgroups wait for slots that never come free before the launch ends, and the step is as long as on
+       one stream (C3, profiles/r04_window_grid_sweep.json: 16 per CU 77.6 ms per step, 24 89.5, 32 89.4; alone the launch takes 2.65 ms at 16 against 2.09 at 32). */
+    P.beside = 16u;
+    if (P.expected_per_strip <= WP_FIT_11_4) { /* w >= 235 at ten candidates per window */
+        /* (lists, round 5: the other stream's emit_list_kernel keeps to two resident workgroups per CU -- sketch_enqueue --
+           and the window stage takes 24 of the 32 wavefront slots: C3 70.7 ms per step against 75.9 at 16 and 82.5 at
+           32, profiles/r05_share_sweep_C3.jsonl) */
+        P.shape = wave == 4 ? WS_4_11_4 : (wave == 16 ? WS_16_11_4 : WS_8_11_4);
+        if (wave != 16 && P.lists) P.beside = 24u;
+    } else if (P.expected_per_strip <= WP_FIT_15_6) { /* w >= 137 */
+        P.shape = WS_8_15_6;
+    } else {                                          /* w >= 94 */
+        /* (dense sketches: the other stream's lookup and map kernels are the longer half of a step, and twelve resident
+           wavefronts per CU beside them make the shortest step -- C5: 8 / 12 / 16 / 24: 304.6 / 288.5 / 315.1 / 318.7 ms) */
+        P.shape = wave == 4 || (c->pipelined && wave != 8) ? WS_4_19_8 : WS_8_19_8;
+        if (P.shape == WS_4_19_8) P.beside = 12u;
+    }
+    if (const char *e = getenv("NTL_SKW_WGS_PER_CU")) P.wgs_per_cu = std::max(1, atoi(e)); /* tuning */
+    if (const char *e = getenv("NTL_SKW_BUDGET")) P.chunk_budget = atoi(e) >= 2 ? (uint32_t)atoi(e) : 0u;
+    return NTL_OK;
+}
+
+/* the 32-bit pass of the plan over the single-run strips (sketch2_kernels.h), on the window stream */
+static void launch_window_pass(ntl_ctx *c, const WindowPlan &P, const Sketch2Args &B)
+{
+    const unsigned strips = B.A.nstrips;
+    const dim3 grid((strips + 7u) & ~7u);
+    switch (P.pass) {
+    case WP_BLOCK_MINIMA:
+        with_constant<0, 16>(P.G.r0, [&](auto r0) {
+            constexpr int R0 = decltype(r0)::value;
+            if (P.nt == 128 && P.big) hipLaunchKernelGGL((sketch_fast_kernel<128, R0, true>), grid, dim3(128), 0, c->wstream, B);
+            else if (P.nt == 128) hipLaunchKernelGGL((sketch_fast_kernel<128, R0, false>), grid, dim3(128), 0, c->wstream, B);
+            else if (P.big) hipLaunchKernelGGL((sketch_fast_kernel<SK_NT, R0, true>), grid, dim3(SK_NT), 0, c->wstream, B);
+            else hipLaunchKernelGGL((sketch_fast_kernel<SK_NT, R0, false>), grid, dim3(SK_NT), 0, c->wstream, B);
+        });
+        return;
+    case WP_THRESH:
+        if (P.direct) hipLaunchKernelGGL((sketch_thresh_kernel<256, true>), grid, dim3(256), 0, c->wstream, B);
+        else hipLaunchKernelGGL((sketch_thresh_kernel<256, false>), grid, dim3(256), 0, c->wstream, B);
+        break;
+    case WP_WAVE:
+        /* resident wavefronts that walk over their strips: as many workgroups as the device holds at once (a multiple of 8: one share of the strips per XCD) */
+        with_wave_kernel(P.shape, [&](auto kern, unsigned threads) {
+            int &per_cu = c->occ[(const void *)kern];
+            if (!per_cu) per_cu = occupancy_blocks(kern, (int)threads);
+            int use = c->pipelined ? std::min(per_cu, (int)(P.beside / (threads / 64u))) : per_cu;
+            if (P.wgs_per_cu) use = std::min(per_cu, P.wgs_per_cu);
+            unsigned wgs = (unsigned)std::max(1, use) * (unsigned)std::max(1, c->n_cu);
+            wgs = std::min(wgs, (strips + threads / 64u - 1u) / (threads / 64u));
+            wgs = (wgs + 7u) & ~7u;
+            /* Two streams, NTL_SKW_BUDGET chunks per wavefront: short-lived workgroups, as many as it takes, that fill what
+               the other stream's kernels leave free (those have the higher stream priority and a bounded number of
+               resident workgroups: sketch_enqueue, emit) -- and the whole CU while that stream has nothing to run. */
+            Sketch2Args Bq = B;
+            if (P.chunk_budget) {
+                const unsigned per_xcd_chunks = (((strips + 7u) >> 3) + SKW_CHUNK - 1u) / SKW_CHUNK;
+                const unsigned per_wg = (threads / 64u) * P.chunk_budget;
+                wgs = 8u * ((per_xcd_chunks + per_wg - 1u) / per_wg);
+                Bq.chunk_budget = P.chunk_budget;
+            }
+            ProfSpan sp(c, "sketch_wave", SID_W); /* the window kernel alone (the span "sketch_mask" around this function also holds the block-minima pass) */
+            hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), 0, c->wstream, Bq);
+        });
+        break;
+    default: return;
+    }
+    /* what the threshold and wave kernels gave up (a window without a candidate: 0.7 % of the strips): the block-minima pass over that list */
+    with_constant<0, 16>(P.G.r0, [&](auto r0) {
+        constexpr int R0 = decltype(r0)::value;
+        if (P.big) hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0, true>), dim3(std::min(strips, 4096u)), dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        else hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0>), dim3(std::min(strips, 4096u)), dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+    });
+}
+
 /* Queues one sketch: the window stage on the window stream, count + emit (+ index lookup) on MAIN behind it.  Nothing
  * waits; the minimizer total lands in the sketch's page-locked slot and s->done is recorded behind it.  `cap` = records the
  * arrays hold: a guess from the expected density (sketch_finalize makes the sketch again if the batch was denser), or the
  * exact total on that second round. */
 static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const ntl_index *ix, ntl_sketch *s, uint64_t cap)
 {
-    SketchGeom G;
-    int C, nt, rc;
-    if ((rc = sketch_geometry(c, k, w, G, C, nt))) return rc;
-    const uint64_t nseq = b->nseq;
+    WindowPlan P;
+    int rc;
+    if ((rc = window_plan(c, b, k, w, s->no_lists, P))) return rc;
+    const SketchGeom &G = P.G;
+    const int C = P.C, nt = P.nt;
+    const bool fast = P.fast(), lists = P.lists;
+    const uint64_t nseq = b->nseq, ub_strips = P.strips;
     const int wsid = c->sid(SID_W);
     hipStream_t ws = c->s(wsid), ms = c->stream;
     /* the host runs at most 8 sketches ahead of the device */
@@ -1703,61 +1747,16 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     T.packed = b->packed.as<uint32_t>(); T.seq_base = b->seq_base.as<uint64_t>();
     T.seq_run_first = b->seq_run_first.as<uint32_t>(); T.run_start = b->run_start.as<uint32_t>();
     T.run_len = b->run_len.as<uint32_t>(); T.nseq = (uint32_t)nseq;
-    /* upper bound of the number of strips from the host-side lengths (exact for sequences without
-       non-ACGT bytes): the grid is sized without waiting for the device */
-    uint64_t ub_strips = 0;
-    for (uint64_t i = 0; i < nseq; i++) {
-        const uint64_t len = b->seq_len[i];
-        if (len + 2 > (uint64_t)k + (uint64_t)w) ub_strips += (len - k - w + 2 + (uint64_t)G.NWO - 1) / (uint64_t)G.NWO;
-    }
-    if (ub_strips >= 0x7FFFFFFFull) return fail(c, NTL_EINVAL, "batch too large: too many strips");
-    /* Which window pass, and what it writes.  32-bit fast pass + exact pass over what it flags; the exact pass alone for small windows
-       / huge k.  Where the fast pass is sketch_wave_kernel (94 <= w <= 1135, k <= 64: every window ntLink is run with) the passes write
-       per-strip LISTS of minimizers (sketch_kernels.h, StripLists) and emit_list_kernel reads those; everywhere else, a bitmask of one
-       bit per base and emit_kernel.  NTL_SKETCH_LISTS=0: the bitmask everywhere (A/B, tests). */
-    const bool small = small_window_form(w);
-    bool fast = C == 16 && k <= 16 * SK2_QMAX && G.a + 2 <= SK2_PAD && !small;
-    if (const char *e = getenv("NTL_SKETCH_FAST")) fast = fast && atoi(e) != 0; /* 0: exact pass only (A/B, tests) */
-    Sketch2Args B;
-    memset(&B, 0, sizeof B);
-    B.A.G = G;
-    if (fast) {   /* sketch_thresh_kernel (threshold-sparsified windows) where a strip's candidate list fits: keys below
-                     T = 2^32 * cpw / w are candidates, cpw = 10 of them per window -- fewer and more strips have a window without
-                     one (they take the exact pass: 0.7 % at 10, 2 % at 9), more and the list work grows (profiles/r03p_*).
-                     NTL_SKETCH_THRESH=0: sketch_fast_kernel everywhere; = x: x candidates per window.  Read per call: the tests
-                     switch it inside one process. */
-        const char *e = getenv("NTL_SKETCH_THRESH");
-        double cpw = e ? atof(e) : 10.0;
-        if (cpw == 1.0) cpw = 10.0;
-        /* a strip's expected 4096 cpw / w candidates must fit the list with room for their spread: 402 entries beside
-           the staged keys (w >= 121 at 10 per window), 680 without them (sketch_thresh_kernel<.., DIRECT>: w >= 71) */
-        if (cpw > 0 && nt != 128 && G.a + 2 <= SK2_PAD && 4096.0 * cpw / w <= 580.0) /* (w > 255: sketch_wave_kernel only, wave_form) */
-            B.thresh = (uint32_t)std::min(4294967295.0, 4294967296.0 * cpw / w);
-        if (const char *e2 = getenv("NTL_SKETCH_ABLATE")) B.dbg = atoi(e2); /* tools/sketch_bench.py only: results are wrong */
-        if (const char *e2 = getenv("NTL_SKETCH_FORCE_REDO")) B.force_redo = atoi(e2); /* tests: every strip takes both passes */
-    }
     StripLists Ls;
     memset(&Ls, 0, sizeof Ls);
     DevBuf lcnt, lent, loff;
-    bool lists = fast && nseq && ub_strips && !s->no_lists && wave_form(B, nt) != 0;
-    if (const char *e = getenv("NTL_SKETCH_LISTS")) lists = lists && atoi(e) != 0;
     if (lists) {
-        /* a slot holds the expected 2 NWO / (w + 1) minimizers of a strip with room for their spread (what does not fit -- low-complexity
-           sequence -- lives in the pool behind the slots); the pool: 32 entries per strip, at least a million */
-        const double mean = 2.0 * (double)G.NWO / (double)(w + 1);
-        uint64_t slot = ((uint64_t)(mean * 1.25 + 24.0) + 15u) & ~(uint64_t)15u;
-        if (const char *e = getenv("NTL_LIST_SLOT")) slot = std::max<uint64_t>(1, (uint64_t)atoll(e)); /* tests: force strips into the pool */
-        uint64_t pool = std::max<uint64_t>((uint64_t)1 << 20, 32 * ub_strips);
-        if (const char *e = getenv("NTL_LIST_POOL")) pool = (uint64_t)atoll(e);                      /* tests: make the pool run out */
-        if ((ub_strips + 1) * slot + pool >= 0xFFFFFFF0ull) lists = false; /* (entries are addressed with 32 bits) */
-        else {
-            Ls.slot = (uint32_t)slot; Ls.ovf_base = (uint32_t)((ub_strips + 1) * slot); Ls.ovf_cap = (uint32_t)pool;
-            /* cnt[ub_strips + 1] (+ the two control words behind it), zeroed: a strip nobody lists has none */
-            if ((rc = lcnt.alloc(c, (ub_strips + 4) * 4, wsid)) || (rc = lent.alloc(c, ((ub_strips + 1) * slot + pool) * 4, wsid)) ||
-                (rc = loff.alloc(c, (ub_strips + 2) * 4))) return rc;
-            lcnt.touch(SID_MAIN); lent.touch(SID_MAIN);
-            Ls.cnt = lcnt.as<uint32_t>(); Ls.ent = lent.as<uint32_t>(); Ls.ctl = Ls.cnt + ub_strips + 2;
-        }
+        Ls.slot = P.slot; Ls.ovf_base = (uint32_t)((ub_strips + 1) * P.slot); Ls.ovf_cap = P.pool;
+        /* cnt[ub_strips + 1] (+ the two control words behind it), zeroed: a strip nobody lists has none */
+        if ((rc = lcnt.alloc(c, (ub_strips + 4) * 4, wsid)) || (rc = lent.alloc(c, ((ub_strips + 1) * P.slot + P.pool) * 4, wsid)) ||
+            (rc = loff.alloc(c, (ub_strips + 2) * 4))) return rc;
+        lcnt.touch(SID_MAIN); lent.touch(SID_MAIN);
+        Ls.cnt = lcnt.as<uint32_t>(); Ls.ent = lent.as<uint32_t>(); Ls.ctl = Ls.cnt + ub_strips + 2;
     }
     /* the fast pass's counters and lists: [0] strips for the exact pass, [1] strips the threshold pass gave up, then the eight chunk
        counters of sketch_wave_kernel (one per XCD's share of the strips, 64 bytes apart), then the two lists.  Zeroed -- with the
@@ -1812,7 +1811,10 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
         A.redo_list = nullptr; A.redo_count = nullptr; A.redo_out = nullptr;
         A.Ls = Ls;
         if (fast) {
+            Sketch2Args B;
+            memset(&B, 0, sizeof B);
             B.A = A;
+            B.thresh = P.thresh; B.dbg = P.dbg; B.force_redo = P.force_redo;
             B.redo_count = redo.as<uint32_t>(); B.fb_count = redo.as<uint32_t>() + 1;
             B.chunk_next = redo.as<uint32_t>() + 16;
             B.redo_list = redo.as<uint32_t>() + redo_head; B.fb_list = B.redo_list + ub_strips + 2;
@@ -1842,8 +1844,7 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
             }
             {
                 ProfSpan sp(c, "sketch_mask", wsid);
-                if (nt == 128) launch_fast_r0<128, 0>(c, B, (unsigned)ub_strips);
-                else launch_fast_r0<SK_NT, 0>(c, B, (unsigned)ub_strips);
+                launch_window_pass(c, P, B);
                 HIPCHK(c, hipGetLastError());
             }
             ProfSpan sp(c, "sketch_redo", wsid);
@@ -1857,7 +1858,7 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
             HIPCHK(c, hipGetLastError());
         } else {
             ProfSpan sp(c, "sketch_mask", wsid);
-            if (small) launch_small_w<2>(c, A, (unsigned)ub_strips, b->any_multi);
+            if (P.pass == WP_SMALL) launch_small(c, A, (unsigned)ub_strips, b->any_multi);
             else if (C == 16) launch_mask<16>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
             else if (C == 4) launch_mask<4>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
             else launch_mask<1>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
@@ -1932,10 +1933,9 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
                grids (profiles/r04_share_sweep_C5.jsonl); the tag form (C3) is as fast uncapped (74.4-75.0 against 74.9-75.9) */
             /* emit_list_kernel (44 registers, 13 KB of LDS) would fill all 32 wavefront slots of a CU, and the window stage's resident
                workgroups of the next sub-batch then wait for them to drain (C3: 91 ms per step uncapped, 75.9 at two per CU) */
-            /* beside the DENSE window shapes (w < 137: twelve window wavefronts per CU, launch_fast_r0) the tag form takes four: C2
+            /* beside the DENSE window shapes (w < 137: twelve window wavefronts per CU, window_plan) the tag form takes four: C2
                0.890 -> 0.800 ms per step (0.806 at three, 0.815 uncapped; profiles/r07b_C2_share_sweep.txt) */
-            const bool dense_windows = fast && B.thresh && 4096.0 * (double)B.thresh / 4294967296.0 > 300.0;
-            int per_cu = !c->pipelined ? 0 : (probe == 2 ? 3 : (lists ? (dense_windows ? 4 : 2) : 0));
+            int per_cu = !c->pipelined ? 0 : (probe == 2 ? 3 : (lists ? (P.dense_windows ? 4 : 2) : 0));
             if (const char *e = getenv("NTL_EMIT_WGS_PER_CU")) per_cu = atoi(e);
             const uint64_t cap = (uint64_t)per_cu * (uint64_t)c->n_cu;
             if (per_cu > 0 && cap >= 8 && cap < tiles) { egrid = (unsigned)cap; E.tile_next = tile_next.as<uint32_t>(); }
@@ -1954,7 +1954,7 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
             else if (emit_u >= 2) hipLaunchKernelGGL((emit_list_kernel<2, 2>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
             else hipLaunchKernelGGL((emit_list_kernel<2, 1>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
         } else
-        if (probe == 0 && (eu ? emit_u >= 4 : small)) hipLaunchKernelGGL((emit_kernel<0, 4, NTL_EMIT_DENSE_CAP>), dim3(egrid), dim3(EMIT_NT), 0, ms, E); /* dense sketches: rounds of 8192, four k-mers' loads in flight per thread */
+        if (probe == 0 && (eu ? emit_u >= 4 : P.pass == WP_SMALL)) hipLaunchKernelGGL((emit_kernel<0, 4, NTL_EMIT_DENSE_CAP>), dim3(egrid), dim3(EMIT_NT), 0, ms, E); /* dense sketches: rounds of 8192, four k-mers' loads in flight per thread */
         else if (probe == 0 && emit_u >= 2) hipLaunchKernelGGL((emit_kernel<0, 2>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
         else if (probe == 0) hipLaunchKernelGGL((emit_kernel<0, 1>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
         else if (probe == 1 && emit_u >= 2) hipLaunchKernelGGL((emit_kernel<1, 2>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
@@ -1998,8 +1998,8 @@ static int sketch_run_impl(ntl_ctx *c, const ntl_batch *b, int k, int w, const n
     *out = nullptr;
     (void)hipSetDevice(c->device);
     SketchGeom G;
-    int C, nt, rc;
-    if ((rc = sketch_geometry(c, k, w, G, C, nt))) return rc;
+    int C, nt, rc; bool small;
+    if ((rc = sketch_geometry(c, k, w, G, C, nt, small))) return rc; /* (a window this build cannot sketch: refused before anything is made) */
     ntl_sketch *s = new ntl_sketch();
     s->c = c; s->nseq = b->nseq; s->k = k; s->w = w; s->src_ix = ix;
     s->no_records = no_records && ix;

@@ -1,0 +1,68 @@
+/*
+ * The plan of a sketch's window pass: what window_plan() (ntl_hip.hip) decides once per sketch, before anything is allocated or
+ * launched, and launch_window_pass() and the emit stage of sketch_enqueue() carry out.
+ */
+#pragma once
+#include "sketch2_kernels.h"
+
+/*
+ * Which window pass a sketch runs with no knob set (DESIGN.md 4.1 holds the same table):
+ *
+ *   w = 1; k > 256; w > 1135           sketch_mask_kernel<1 / 16> alone (EXACT_ONLY; <4> and <1> for 2 <= w <= 15 only by knob)
+ *   2 <= w <= 15                       sketch_small_kernel<W>                                                     (SMALL)
+ *   16 <= w < 64                       sketch_fast_kernel<128, R0, true>                                          (BLOCK_MINIMA)
+ *   64 <= w <= 70                      sketch_fast_kernel<256, R0, false>                                         (BLOCK_MINIMA)
+ *   71 <= w <= 93, and
+ *   94 <= w <= 120 when k > 64         sketch_thresh_kernel<256, true> + sketch_fast_list_kernel<256, R0>         (THRESH, direct)
+ *   121 <= w <= 255 when k > 64        sketch_thresh_kernel<256, false> + sketch_fast_list_kernel<256, R0>        (THRESH)
+ *   256 <= w <= 1135 when k > 64       sketch_fast_kernel<256, R0, true>                                          (BLOCK_MINIMA)
+ *   94 <= w <= 1135, k <= 64           sketch_wave_kernel + sketch_fast_list_kernel<256, R0, w > 255>, strip lists (WAVE):
+ *       94 <= w <= 136                     <4, 19, 8> beside the other stream's kernels, <8, 19, 8> alone
+ *       137 <= w <= 234                    <8, 15, 6>
+ *       235 <= w <= 1135                   <8, 11, 4>
+ *
+ * Every 32-bit pass is followed by the exact pass over the strips it flagged.  The w boundaries above 70 are those of the candidates a
+ * strip of 4096 k-mers is expected to hold, 4096 T / 2^32 = 40960 / w at the default ten candidates per window, against:
+ */
+static const double WP_FIT_THRESH = 580.0; /* above: no threshold (sketch_thresh_kernel<.., DIRECT>'s list of 680 with room for the spread) */
+static const double WP_FIT_WAVE = 440.0;   /* above: not sketch_wave_kernel (its largest shape's list: 8 rounds of 64) */
+static const double WP_FIT_STAGED = 340.0; /* above: sketch_thresh_kernel without staged keys (402 entries beside them) */
+static const double WP_FIT_15_6 = 300.0;   /* above: the <.., 19, 8> shapes, and the emit grid beside these DENSE windows takes four workgroups per CU */
+static const double WP_FIT_11_4 = 175.0;   /* above: <8, 15, 6> */
+
+enum WindowPass { WP_SMALL, WP_EXACT_ONLY, /* the 32-bit passes, each with the exact pass over what it flags: */ WP_BLOCK_MINIMA, WP_THRESH, WP_WAVE };
+/* sketch_wave_kernel<wavefronts per workgroup, staging slots per lane, scan rounds>: the slots hold a lane's 64 p candidates + 4.5 sigma,
+   the list (64 per round) a strip's 4096 p + 4 sigma; what does not fit is given up.  The first WS_DEFAULTS are some (k, w)'s default */
+enum WaveShape { WS_8_11_4, WS_8_15_6, WS_8_19_8, WS_4_19_8, WS_DEFAULTS, WS_4_11_4 = WS_DEFAULTS, WS_16_11_4 };
+
+struct WindowPlan {
+    SketchGeom G;
+    int C, nt;             /* k-mers per lane, lanes per strip */
+    uint64_t strips;       /* upper bound from the host-side lengths (exact for sequences without non-ACGT bytes): grids are sized without waiting for the device */
+    WindowPass pass;
+    bool big, direct;      /* BLOCK_MINIMA and the list pass behind WAVE: the kernel's BIG form; THRESH: the variant without staged keys */
+    WaveShape shape;       /* WAVE */
+    unsigned beside;       /* WAVE, two streams: wavefront slots per CU the resident workgroups take beside the other stream's kernels */
+    int wgs_per_cu;        /* WAVE: NTL_SKW_WGS_PER_CU (tuning); 0: from `beside` */
+    uint32_t chunk_budget; /* WAVE: NTL_SKW_BUDGET (0: resident wavefronts; tuning, tools/share_sweep.py) */
+    uint32_t thresh;       /* keys below it are candidates; 0: no threshold */
+    int dbg, force_redo;
+    double expected_per_strip; /* candidates a strip is expected to hold */
+    bool dense_windows;    /* for the emit grid */
+    bool lists;            /* the passes write per-strip lists of minimizers, not the bitmask */
+    uint32_t slot, pool;   /* entries of a strip's list slot / of the pool behind the slots */
+    bool fast() const { return pass >= WP_BLOCK_MINIMA; }
+};
+
+template <typename F>
+static void with_wave_kernel(WaveShape shape, F &&f)
+{
+    switch (shape) {
+    case WS_8_11_4: return f(sketch_wave_kernel<8, 11, 4>, 512u);
+    case WS_8_15_6: return f(sketch_wave_kernel<8, 15, 6>, 512u);
+    case WS_8_19_8: return f(sketch_wave_kernel<8, 19, 8>, 512u);
+    case WS_4_19_8: return f(sketch_wave_kernel<4, 19, 8>, 256u);
+    case WS_4_11_4: return f(sketch_wave_kernel<4, 11, 4>, 256u);
+    case WS_16_11_4: return f(sketch_wave_kernel<16, 11, 4>, 1024u);
+    }
+}

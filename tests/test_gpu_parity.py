@@ -519,14 +519,14 @@ def test_one_stream_and_back(dev):
     pc.check_full_pipeline(dev, contigs, reads, 32, 250, z=1000, sensitive=True)
 
 
-@pytest.mark.parametrize("env", [{"NTL_SKETCH_THRESH": "0"}, {"NTL_SKETCH_THRESH": "0", "NTL_SKETCH_LANES": "1"}, {"NTL_EMIT_U": "2"},
-                                 {"NTL_SKETCH_THRESH": "0", "NTL_SKETCH_LANES": "1", "NTL_EMIT_U": "2"}, {"NTL_SKETCH_THRESH": "5"}, {"NTL_SKETCH_THRESH": "13"},
+@pytest.mark.parametrize("env", [{"NTL_SKETCH_THRESH": "0"}, {"NTL_EMIT_U": "2"},
+                                 {"NTL_SKETCH_THRESH": "0", "NTL_EMIT_U": "2"}, {"NTL_SKETCH_THRESH": "5"}, {"NTL_SKETCH_THRESH": "13"},
                                  {"NTL_SKETCH_WAVE": "0"}, {"NTL_SKETCH_WAVE": "2"}, {"NTL_SKETCH_WAVE": "8"}, {"NTL_SKETCH_WAVE": "9"},
                                  {"NTL_SKETCH_WAVE": "0", "NTL_SKETCH_THRESH": "5"}],
                          ids=lambda e: ",".join(f"{k[4:]}={v}" for k, v in e.items()))
 def test_kernel_variants_full_pipeline(dev, monkeypatch, env):
-    """The window passes that are not the default for 71 <= w <= 255 (sketch_fast_kernel; sketch_lanes_kernel, the experiment of
-    DESIGN 4.12), the threshold pass with other candidate densities than the default, and the two-wide emit kernel on the GPU:
+    """The window pass that is not the default for 71 <= w <= 255 (sketch_fast_kernel), the threshold pass with other candidate
+    densities than the default, and the two-wide emit kernels on the GPU (off the lists, and -- with THRESH=0 -- off the bitmask):
     scaled-down C3- and C5-like workloads, full pipeline against the oracle, and the fuzz sequences."""
     import fuzz_cases
     for k_, v in env.items():

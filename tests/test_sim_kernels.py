@@ -431,10 +431,10 @@ def test_sim_one_stream_and_back(dev):
     pc.check_full_pipeline(dev, contigs, reads, 40, 100, z=1000, sensitive=True)
 
 
-@pytest.mark.parametrize("env", [{"NTL_SKETCH_THRESH": "0"}, {"NTL_SKETCH_THRESH": "0", "NTL_SKETCH_LANES": "1"}, {"NTL_EMIT_U": "2"},
+@pytest.mark.parametrize("env", [{"NTL_SKETCH_THRESH": "0"}, {"NTL_EMIT_U": "2"},
                                  {"NTL_SKETCH_THRESH": "4"}, {"NTL_SKETCH_THRESH": "13"}])
 def test_sim_kernel_variants_full_pipeline(dev, monkeypatch, env):
-    """The window passes that are not the default for 71 <= w <= 255 (sketch_fast_kernel, sketch_lanes_kernel), the threshold
+    """The window pass that is not the default for 71 <= w <= 255 (sketch_fast_kernel), the threshold
     pass with few candidates per window (most strips have a window without one and take the exact pass) and with many, and the
     emit kernel with two minimizers in flight per thread: same records as the oracle on fixtures, fuzz sequences (ties, N
     patterns) and windows of both 20-KB ranges."""

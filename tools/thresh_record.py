@@ -12,7 +12,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 tag = sys.argv[1]
 src = os.path.join(ROOT, "gpurun_out", tag)
-KERNELS = ("sketch_thresh_kernel", "sketch_fast_kernel", "sketch_lanes_kernel")
+KERNELS = ("sketch_thresh_kernel", "sketch_fast_kernel", "sketch_lanes_kernel")  # (the last: in round-3 traces only; the experiment's code has left the tree)
 
 
 def counters(path):
