@@ -179,17 +179,26 @@ typedef __attribute__((address_space(3))) const uint64_t ntl_lds_cu64;
 /* hides a value's origin from the optimiser (no instruction) */
 #define NTL_OPAQUE(v) asm volatile("" : "+v"(v))
 
-/* *p++ = (v & ~mask) | T for a pointer into LDS and a constant T <= 64, as the three instructions it is: v_bfi_b32 with T as an
+/* *p++ = (v & ~mask) | T for a pointer into LDS and a constant T, as the three vector instructions it is: v_bfi_b32 with T as an
    inline constant, ds_write_b32, v_add_u32 (the compiler makes a v_mov of the constant, a temporary of the incremented pointer
-   and a v_mov of that).  The write is not in the compiler's count of outstanding LDS operations; LDS operations of a wavefront
-   complete in order, so a wait the compiler computes for one of ITS reads can only come out stricter, never laxer. */
+   and a v_mov of that).  T > 64 is no inline constant, and a VOP3 instruction takes no literal on this architecture: such a T comes
+   from a scalar register loaded right there (s_mov_b32: the scalar unit's issue slot, not the vector ALU's, and nothing for the
+   compiler to hoist and keep a register per step for).  The write is not in the compiler's count of outstanding LDS operations; LDS
+   operations of a wavefront complete in order, so a wait the compiler computes for one of ITS reads can only come out stricter,
+   never laxer. */
 template <int T>
 __device__ __forceinline__ void ntl_lds_push_tagged(uint32_t *&p, uint32_t mask, uint32_t v)
 {
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
     lds_u32 *q = (lds_u32 *)p;
     uint32_t tmp;
-    asm volatile("v_bfi_b32 %1, %2, %3, %4\n\tds_write_b32 %0, %1\n\tv_add_u32 %0, 4, %0" : "+v"(q), "=&v"(tmp) : "v"(mask), "n"(T), "v"(v) : "memory");
+    if constexpr (T <= 64) {
+        asm volatile("v_bfi_b32 %1, %2, %3, %4\n\tds_write_b32 %0, %1\n\tv_add_u32 %0, 4, %0" : "+v"(q), "=&v"(tmp) : "v"(mask), "n"(T), "v"(v) : "memory");
+    } else {
+        uint32_t st;
+        asm volatile("s_mov_b32 %2, %4\n\tv_bfi_b32 %1, %3, %2, %5\n\tds_write_b32 %0, %1\n\tv_add_u32 %0, 4, %0"
+                     : "+v"(q), "=&v"(tmp), "=&s"(st) : "v"(mask), "n"(T), "v"(v) : "memory");
+    }
     p = (uint32_t *)q;
 }
 

@@ -35,6 +35,7 @@
 
 #define NTL_END_PAD 4096u /* bases of padding behind the last sequence (rolling over-reads) */
 #define SK_NT 256
+#define SK_NT_LONG 512 /* lanes of 16 k-mers of the 8192-ordinal strips (window_plan) */
 #define NTL_MAX_W (16 * (SK_NT - 4) + 31) /* 16 k-mers per lane, a + 2 <= SK_NT - 2 halo lanes: w <= 4063 */
 
 /* ------------------------------------------------------------------ context ------------- */
@@ -1432,6 +1433,7 @@ static void launch_mask(ntl_ctx *c, const SketchArgs &A, unsigned strips, bool s
     /* 16 k-mers per lane: one instantiation per strip width, R0 at run time (this is the redo / multi-run pass since the 32-bit
        window pass took over the common case); 4 and 1 k-mers per lane (w < 16): R0 as a template parameter */
     if (C == 16 && nt == 128) launch_mask_r0<C, 128, -1>(c, A, strips, single, multi);
+    else if (C == 16 && nt == SK_NT_LONG) { if constexpr (C == 16) launch_mask_r0<16, SK_NT_LONG, -1>(c, A, strips, single, multi); }
     else if (C == 16) launch_mask_r0<C, SK_NT, -1>(c, A, strips, single, multi);
     else with_constant<0, C>(A.G.r0, [&](auto r0) { launch_mask_r0<C, SK_NT, decltype(r0)::value>(c, A, strips, single, multi); });
 }
@@ -1523,8 +1525,9 @@ static void launch_small(ntl_ctx *c, const SketchArgs &A, unsigned strips, bool 
 
 /* geometry of the window pass for (k, w): k-mers per lane, lanes per strip.  `small`: it runs as sketch_small_kernel (2 <= w <= 15: the
    stages around `pair`); NTL_SKETCH_SMALL=0, or any setting of the k-mers-per-lane knob: the round-1 forms with four / one k-mer per
-   lane (A/B, tests).  The knobs are read per call: the tests switch them inside one process. */
-static int sketch_geometry(ntl_ctx *c, int k, int w, SketchGeom &G, int &C, int &nt, bool &small)
+   lane (A/B, tests).  The knobs are read per call: the tests switch them inside one process.  long_strips: window_plan's second call,
+   for strips of SK_NT_LONG lanes (w >= 16, sixteen k-mers per lane). */
+static int sketch_geometry(ntl_ctx *c, int k, int w, SketchGeom &G, int &C, int &nt, bool &small, bool long_strips = false)
 {
     if (k < 1 || k > 4096 || w < 1) return fail(c, NTL_EINVAL, "k must be in 1..4096 and w >= 1");
     C = w >= 16 ? 16 : (w >= 4 ? 4 : 1);
@@ -1552,6 +1555,7 @@ static int sketch_geometry(ntl_ctx *c, int k, int w, SketchGeom &G, int &C, int 
         const int v = atoi(e);
         if ((v == 256 || (v == 128 && C == 16)) && v - (G.a + 2) >= 2) nt = v;
     }
+    if (long_strips && C == 16) nt = SK_NT_LONG;
     G.LW = nt - (G.a + 2);
     if (G.LW < 2 && C != 16) { /* a tuning knob (NTL_SKETCH_C) made the strip too short for this window: back to the default */
         C = 16;
@@ -1579,10 +1583,14 @@ static int window_plan(ntl_ctx *c, const ntl_batch *b, int k, int w, bool no_lis
     int rc;
     if ((rc = sketch_geometry(c, k, w, P.G, P.C, P.nt, small))) return rc;
     const SketchGeom &G = P.G;
-    for (uint64_t i = 0; i < b->nseq; i++) {
-        const uint64_t len = b->seq_len[i];
-        if (len + 2 > (uint64_t)k + (uint64_t)w) P.strips += (len - k - w + 2 + (uint64_t)G.NWO - 1) / (uint64_t)G.NWO;
-    }
+    auto count_strips = [&]() {
+        P.strips = 0;
+        for (uint64_t i = 0; i < b->nseq; i++) {
+            const uint64_t len = b->seq_len[i];
+            if (len + 2 > (uint64_t)k + (uint64_t)w) P.strips += (len - k - w + 2 + (uint64_t)G.NWO - 1) / (uint64_t)G.NWO;
+        }
+    };
+    count_strips();
     if (P.strips >= 0x7FFFFFFFull) return fail(c, NTL_EINVAL, "batch too large: too many strips");
     /* 32-bit fast pass + exact pass over what it flags; the exact pass alone for small windows / huge k */
     bool fast = P.C == 16 && k <= 16 * SK2_QMAX && G.a + 2 <= SK2_PAD && !small;
@@ -1598,7 +1606,7 @@ static int window_plan(ntl_ctx *c, const ntl_batch *b, int k, int w, bool no_lis
     if (cpw > 0 && P.nt != 128 && 4096.0 * cpw / w <= WP_FIT_THRESH) P.thresh = (uint32_t)std::min(4294967295.0, 4294967296.0 * cpw / w);
     if (const char *e = getenv("NTL_SKETCH_ABLATE")) P.dbg = atoi(e); /* tools/sketch_bench.py only: results are wrong */
     if (const char *e = getenv("NTL_SKETCH_FORCE_REDO")) P.force_redo = atoi(e); /* tests: every strip takes both passes */
-    P.expected_per_strip = 4096.0 * (double)P.thresh / 4294967296.0;
+    P.expected_per_strip = 4096.0 * (double)P.thresh / 4294967296.0; /* (per 4096 k-mers whatever the strip length: what the WP_FIT_* bounds are written for) */
     P.dense_windows = P.expected_per_strip > WP_FIT_15_6;
     const bool sparse = P.thresh && (P.dbg & ~24) == 0; /* (ablation bits 8 and 16 exist in the threshold and wave kernels too) */
     /* one wavefront per strip, 64 k-mers per lane (sketch_wave_kernel) where a lane's first k-mer lies in its own 64 bases and a strip's
@@ -1618,6 +1626,24 @@ static int window_plan(ntl_ctx *c, const ntl_batch *b, int k, int w, bool no_lis
         P.big = G.a + 2 > 16 || w < 64;
     }
     if (P.pass != WP_WAVE) return NTL_OK;
+    /* The strip length, one per sketch: every table, list and pass of it is made for P.nt lanes of 16 k-mers.  8192 ordinals -- 128
+       k-mers per lane of sketch_wave_kernel, which halves what it pays per strip (the first k-mers from the tables, header, sentinels,
+       window 0, the list's place) and the halo of w + 15 elements that two strips both roll -- exist for the windows whose
+       4096-ordinal shape is <8, 11, 4>, and are NOT the default: measured on C3 (profiles/HISTORY.md, "8192-ordinal strips") the long
+       shape issues 9 % fewer vector instructions per base, but alone its 24 wavefronts per CU are only 2.4 % faster than the short
+       shape's 32 (1.80 against 1.84 ms per launch: under the 3 % that tells a gain from the boxes' wander), and beside the other
+       stream's kernels, where both run 24, the step takes 60.2 ms against 58.0: 4096 won on both paths.  NTL_SKETCH_STRIP=8192: the long strips wherever they exist; 4096: the short ones (A/B, tests). */
+    const bool long_range = P.expected_per_strip <= WP_FIT_11_4 && wave != 4 && wave != 16; /* (those two: A/B shapes of the short strips) */
+    bool long_strips = false;
+    if (const char *e = getenv("NTL_SKETCH_STRIP")) {
+        const int v = atoi(e);
+        if (v == 4096) long_strips = false;
+        else if (v == 8192) long_strips = long_range;
+    }
+    if (long_strips) {
+        if ((rc = sketch_geometry(c, k, w, P.G, P.C, P.nt, small, true))) return rc;
+        count_strips();
+    }
     /* Where the fast pass is sketch_wave_kernel (every window ntLink is run with) the passes write per-strip LISTS of minimizers
        (sketch_kernels.h, StripLists) and emit_list_kernel reads those; everywhere else, a bitmask of one bit per base and emit_kernel.
        NTL_SKETCH_LISTS=0: the bitmask everywhere (A/B, tests). */
@@ -1638,7 +1664,10 @@ static int window_plan(ntl_ctx *c, const ntl_batch *b, int k, int w, bool no_lis
        CU's 32 slots: with more, those kernels' workgroups wait for slots that never come free before the launch ends, and the step is as long as on
        one stream (C3, profiles/r04_window_grid_sweep.json: 16 per CU 77.6 ms per step, 24 89.5, 32 89.4; alone the launch takes 2.65 ms at 16 against 2.09 at 32). */
     P.beside = 16u;
-    if (P.expected_per_strip <= WP_FIT_11_4) { /* w >= 235 at ten candidates per window */
+    if (P.nt == SK_NT_LONG) { /* w >= 235, strips of 8192 */
+        P.shape = WS_8_19_7_L128;
+        if (P.lists) P.beside = 24u;
+    } else if (P.expected_per_strip <= WP_FIT_11_4) { /* w >= 235 at ten candidates per window */
         /* (lists, round 5: the other stream's emit_list_kernel keeps to two resident workgroups per CU -- sketch_enqueue --
            and the window stage takes 24 of the 32 wavefront slots: C3 70.7 ms per step against 75.9 at 16 and 82.5 at
            32, profiles/r05_share_sweep_C3.jsonl) */
@@ -1705,8 +1734,11 @@ static void launch_window_pass(ntl_ctx *c, const WindowPlan &P, const Sketch2Arg
     /* what the threshold and wave kernels gave up (a window without a candidate: 0.7 % of the strips): the block-minima pass over that list */
     with_constant<0, 16>(P.G.r0, [&](auto r0) {
         constexpr int R0 = decltype(r0)::value;
-        if (P.big) hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0, true>), dim3(std::min(strips, 4096u)), dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
-        else hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0>), dim3(std::min(strips, 4096u)), dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        const dim3 lgrid(std::min(strips, 4096u));
+        if (P.nt == SK_NT_LONG && P.big) hipLaunchKernelGGL((sketch_fast_list_kernel<SK_NT_LONG, R0, true>), lgrid, dim3(SK_NT_LONG), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        else if (P.nt == SK_NT_LONG) hipLaunchKernelGGL((sketch_fast_list_kernel<SK_NT_LONG, R0>), lgrid, dim3(SK_NT_LONG), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        else if (P.big) hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0, true>), lgrid, dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        else hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0>), lgrid, dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
     });
 }
 

@@ -845,18 +845,22 @@ __global__ __launch_bounds__(NT) void sketch_thresh_kernel(Sketch2Args B)
 
 /*
  * sketch_wave_kernel: the threshold pass (see sketch_thresh_kernel above for the algorithm and its proof) with ONE WAVEFRONT PER
- * STRIP, 64 k-mers per lane, and wavefronts that stay resident and walk over their strips -- round 4.
+ * STRIP, CL = 64 k-mers per lane (below: the numbers of this form) or 128, and wavefronts that stay resident and walk over their
+ * strips -- round 4.
  *
- * Same strips (4096 consecutive valid-k-mer ordinals, strip_table_kernel's geometry for NT = 256, C = 16), same keys, same
+ * Same strips (64 CL = 4096 or 8192 consecutive valid-k-mer ordinals, strip_table_kernel's geometry for NT = 256 or 512, C = 16: the
+ * sketch has ONE strip length, WindowPlan::nt, and every pass and every list of it is made for that), same keys, same
  * candidates, same decision per candidate, same lists for the passes behind it; so a strip it gives up is taken over by
- * sketch_fast_list_kernel exactly as before.  What differs is who does the work:
+ * sketch_fast_list_kernel exactly as before.  CL = 128 pays what is paid per strip (the first k-mers out of the tables, the strip's
+ * header, the sentinels, window 0, the list's place, the w + 15 elements two strips both roll) once per 8192 k-mers; it takes S = 19
+ * slots per lane, seven list rounds, a seventh tag bit and 5.2 KB of LDS per wavefront.  What differs is who does the work:
  *
  *   - a lane owns 64 consecutive k-mers instead of 16: the first k-mer's hash (the table lookups, the combination of the 16-base
  *     partial hashes) is paid once per 64 k-mers, and for k <= 64 it is made from the lane's OWN bases -- no exchange of partial
  *     hashes or base words between lanes, no exchange area in LDS;
  *   - the keys are never stored: each key is tested against the threshold as it leaves the rolling step, and a candidate is
  *     written at once into the lane's own staging slots (S per lane: a lane holds 64 p = 2.6 candidates on average at ten per
- *     window of 250) as ONE word: the key with its six low bits replaced by the step t it was made in (SKW_NEAR below); the lanes
+ *     window of 250) as ONE word: the key with its six low bits replaced by the step t it was made in (skw_near below); the lanes
  *     then take their staged candidates into registers and write them back, in position order, over the same words -- staging
  *     area and list of keys are one array -- with the positions 64 L + t as words at a constant distance behind them: 4 KB of LDS
  *     per wavefront, so that a CU holds 32 of them;
@@ -872,9 +876,9 @@ __global__ __launch_bounds__(NT) void sketch_thresh_kernel(Sketch2Args B)
  *   - hand-offs between lanes (the list, the sentinels) are wave-synchronous LDS traffic (ntl_wave_sync: ordering only).
  *
  * Elements: local position p = 64 L + t of the strip is ordinal E0 + p; p = 0 belongs to the previous strip's windows only
- * and positions >= hi = min(4096, M - E0) lie behind the sequence: candidates found there are dropped when the list is made.
+ * and positions >= hi = min(64 CL, M - E0) lie behind the sequence: candidates found there are dropped when the list is made.
  * Gives the strip up (B.fb_list) when a lane stages more than S candidates, the list would hold more than 64 ROUNDS - 8, or the
- * scans say so (a window without a candidate, a near tie, a key within SKW_NEAR of the threshold).  Round 6: one pass over the list
+ * scans say so (a window without a candidate, a near tie, a key within skw_near of the threshold).  Round 6: one pass over the list
  * decides which candidates scan at all (below: "who has to scan"), and the window may be anything up to the block-minima pass's 1135
  * k-mers -- it only enters the scans as a distance (the workgroup-per-strip passes' a + 2 <= 16 lanes is not this kernel's limit).
  * Soaked against the oracle on
@@ -890,54 +894,116 @@ __device__ __forceinline__ uint4 skw_strip_load(const StripLite *tab, uint32_t s
     return v;
 }
 
-/* k-mers per lane of a strip of `hi` elements: 64, or -- a sequence's last strip -- the multiple of 16 that still covers it: the
-   wavefront rolls 16, 32 or 48 steps instead of 64, all lanes at work (round 5; a tail strip used to roll 64 steps with the lanes
-   behind the sequence's end idle: 15 % of all lane-steps at C3; blocks of eight steps instead of sixteen: no shorter, 2.114 against
-   2.102 ms per C3 launch) */
+/* k-mers per lane of a strip of `hi` elements: all CL = 64 or 128 of them, or -- a sequence's last strip -- the multiple of 16 that
+   still covers it: the wavefront rolls 16, 32, ... steps instead of CL, all lanes at work (round 5; a tail strip used to roll 64 steps
+   with the lanes behind the sequence's end idle: 15 % of all lane-steps at C3; blocks of eight steps instead of sixteen: no shorter,
+   2.114 against 2.102 ms per C3 launch).  hi <= 64 CL, so the result is at most CL: one expression for both strip lengths. */
 __device__ __forceinline__ uint32_t skw_per_lane(uint32_t hi_raw)
 {
     const uint32_t hi = hi_raw & 0xFFFFu;
-    return hi > 3072u ? 64u : ((hi + 1023u) >> 10) << 4;
+    return ((hi + 1023u) >> 10) << 4;
 }
 
+/* the words of `packed` that hold the first of a lane's bases that leave (wi) and of those that enter, k bases further on (wq), and the
+   bit offsets of the two inside them.  wmax = the last word - 9: a lane reads the nine words wi .. wi + 8 at most */
+__device__ __forceinline__ void skw_words_at(const uint4 I, int L, int k, uint32_t wmax, uint32_t &wi, uint32_t &wq, uint32_t &ao, uint32_t &ai)
+{
+    const uint64_t gp = (((uint64_t)I.y << 32) | I.x) + (uint64_t)((uint32_t)L * skw_per_lane(I.z));
+    const uint64_t gq = gp + (uint64_t)k;
+    wi = (uint32_t)(gp >> 4); wq = (uint32_t)(gq >> 4);
+    wi = wi < wmax ? wi : wmax; /* over-reads behind the last sequence: values never used */
+    wq = wq < wmax ? wq : wmax;
+    ao = 2u * ((uint32_t)gp & 15u); ai = 2u * ((uint32_t)gq & 15u);
+}
+
+/* words 0 .. 4 on either side: the first 64 k-mers of a lane */
 __device__ __forceinline__ SkwWords skw_words_load(const uint32_t *__restrict__ packed, const uint4 I, int L, int k, uint32_t wmax)
 {
     SkwWords W;
-    const uint64_t gp = (((uint64_t)I.y << 32) | I.x) + (uint64_t)((uint32_t)L * skw_per_lane(I.z));
-    const uint64_t gq = gp + (uint64_t)k;
-    uint32_t wi = (uint32_t)(gp >> 4), wq = (uint32_t)(gq >> 4);
-    wi = wi < wmax ? wi : wmax; /* over-reads behind the last sequence: values never used */
-    wq = wq < wmax ? wq : wmax;
+    uint32_t wi, wq;
+    skw_words_at(I, L, k, wmax, wi, wq, W.ao, W.ai);
     W.o0 = ntl_load4_a4(packed + wi); W.o4 = packed[wi + 4];
     W.i0 = ntl_load4_a4(packed + wq); W.i4 = packed[wq + 4];
-    W.ao = 2u * ((uint32_t)gp & 15u); W.ai = 2u * ((uint32_t)gq & 15u);
     return W;
 }
 
-/* A staged key carries the step it was made in in its six low bits: k' = (key & ~63) | t.  Two such words order their k-mers' hashes
-   when they are more than SKW_NEAR apart: k'_j - k'_i > SKW_NEAR  =>  key_j - key_i > SKW_NEAR - 126 >= SK2_NEAR  =>  h0_i < h0_j
-   ("exact" in the header of this file); closer pairs are the near ties that give a strip up -- 2^-23 per window instead of 2^-29. */
+/* words 5 .. 8 on either side: k-mers 64 .. 127 of a lane of an 8192-ordinal strip.  Asked for in front of the strip's rolling loop and
+   used behind its first half: they are never live together with the next strip's words, which are asked for behind the loop */
+struct SkwWords2 { uint4 o5, i5; };
+
+__device__ __forceinline__ SkwWords2 skw_words2_load(const uint32_t *__restrict__ packed, const uint4 I, int L, int k, uint32_t wmax)
+{
+    SkwWords2 H;
+    uint32_t wi, wq, ao, ai;
+    skw_words_at(I, L, k, wmax, wi, wq, ao, ai);
+    H.o5 = ntl_load4_a4(packed + wi + 5);
+    H.i5 = ntl_load4_a4(packed + wq + 5);
+    return H;
+}
+
+/* A staged key carries the step it was made in in its low bits, six of them for CL = 64 k-mers per lane, seven for 128:
+   k' = (key & ~(CL - 1)) | t.  Two such words order their k-mers' hashes when they are more than NEAR = skw_near<CL>() apart:
+   k'_j - k'_i > NEAR  =>  key_j - key_i > NEAR - 2 (CL - 1) >= SK2_NEAR  =>  h0_i < h0_j  ("exact" in the header of this file);
+   closer pairs are the near ties that give a strip up -- 2^-23 per window at CL = 64, 2^-22 at 128, instead of 2^-29. */
 #define SKW_CHUNK 4u /* strips a wavefront takes from its XCD's counter at a time */
-#define SKW_NEAR 131u
-static_assert(SKW_NEAR >= 126u + SK2_NEAR, "see above");
+template <int CL>
+constexpr uint32_t skw_near() { return CL == 64 ? 131u : 2u * (uint32_t)(CL - 1) + SK2_NEAR; }
+static_assert(skw_near<64>() >= 2u * 63u + SK2_NEAR && skw_near<128>() >= 2u * 127u + SK2_NEAR, "see above");
 
 /* rolling step T (the k-mer at position T of the lane's block from the one before it) and its candidate test */
 template <int T>
-__device__ __forceinline__ void skw_step(uint32_t &fx, uint32_t &ry, uint32_t &fd, const uint2 sd, uint32_t tm1, uint32_t low6, uint32_t *&dst)
+__device__ __forceinline__ void skw_step(uint32_t &fx, uint32_t &ry, uint32_t &fd, const uint2 sd, uint32_t tm1, uint32_t tagm, uint32_t *&dst)
 {
     fx = ntl_alignbit(fx, fd, 31) ^ sd.x; /* srol1 on the ring: (fx << 1) | ring bit 30, which is the top bit of fd = fx << 1 */
     const uint32_t a = ry ^ sd.y;
     ry = ntl_alignbit(a >> 1, a, 1);      /* sror1: ring bit 0 (bit 1 of a) -> bit 31 */
     fd = ntl_double(fx); /* fx << 1 as fx + fx: v_add_u32 issues in 2.4 cycles, v_lshlrev_b32 in 4.4 (profiles/valu_cycles.json) */
     const uint32_t key = fd + ry;
-    if (key <= tm1) ntl_lds_push_tagged<T>(dst, low6, key);
+    if (key <= tm1) ntl_lds_push_tagged<T>(dst, tagm, key);
 }
 
 template <int T0, int... J>
 __device__ __forceinline__ void skw_steps(std::integer_sequence<int, J...>, uint32_t &fx, uint32_t &ry, uint32_t &fd, const uint2 (&sd)[8], uint32_t tm1,
-                                          uint32_t low6, uint32_t *&dst)
+                                          uint32_t tagm, uint32_t *&dst)
 {
-    (skw_step<T0 + J>(fx, ry, fd, sd[J], tm1, low6, dst), ...);
+    (skw_step<T0 + J>(fx, ry, fd, sd[J], tm1, tagm, dst), ...);
+}
+
+/* block M of a lane's rolling: the sixteen steps 16 M + 1 .. 16 M + 16 (the last block of CL k-mers: fifteen) over the sixteen bases
+   `so` that leave and `si` that enter */
+template <int M, int CL>
+__device__ __forceinline__ void skw_block(const uint32_t so, const uint32_t si, const uint32_t *s_roll, uint32_t &fx, uint32_t &ry, uint32_t &fd,
+                                          uint32_t tm1, uint32_t tagm, uint32_t *&dst)
+{
+    /* byte offset into s_roll of step b + 1 of the block: 8 * (in<<2 | out) for base b of si / so, as byte b/4 of word b%4 */
+    uint32_t wz[4];
+#pragma unroll
+    for (int r = 0; r < 4; r++) {
+        const uint32_t o2 = r < 2 ? so << (3 - 2 * r) : so >> (2 * r - 3);
+        const uint32_t i2 = r < 3 ? si << (5 - 2 * r) : si >> (2 * r - 5);
+        wz[r] = (o2 & 0x18181818u) | (i2 & 0x60606060u);
+    }
+    /* the seed pairs of eight steps are requested together, in front of the steps: every step ends in a predicated
+       write (a basic block of its own), and a read issued inside a step would be waited for inside it */
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        uint2 sd[8];
+#pragma unroll
+        for (int b = 8 * h; b < 8 * h + 8; b++) {
+            const uint32_t off = ntl_bfe(wz[b & 3], 8u * (uint32_t)(b >> 2), 8u);
+            sd[b & 7] = ntl_lds_load2_ordered((const uint2 *)((const char *)s_roll + off));
+        }
+        if (h == 0) skw_steps<16 * M + 1>(std::make_integer_sequence<int, 8>(), fx, ry, fd, sd, tm1, tagm, dst);
+        else skw_steps<16 * M + 9>(std::make_integer_sequence<int, (16 * M + 16 < CL ? 8 : 7)>(), fx, ry, fd, sd, tm1, tagm, dst);
+    }
+}
+
+/* block m, a number that is known once the loop around the call is unrolled */
+template <int CL, int... M>
+__device__ __forceinline__ void skw_block_at(std::integer_sequence<int, M...>, const int m, const uint32_t so, const uint32_t si, const uint32_t *s_roll,
+                                             uint32_t &fx, uint32_t &ry, uint32_t &fd, uint32_t tm1, uint32_t tagm, uint32_t *&dst)
+{
+    ((m == M ? (skw_block<M, CL>(so, si, s_roll, fx, ry, fd, tm1, tagm, dst), 0) : 0), ...);
 }
 
 /* wavefronts per SIMD a shape is compiled for = what its LDS lets a CU hold (the register budget follows from it): the shapes of the
@@ -945,10 +1011,15 @@ __device__ __forceinline__ void skw_steps(std::integer_sequence<int, J...>, uint
 template <int WAVES, int S>
 constexpr int skw_waves_per_simd() { return S >= 15 ? (WAVES >= 8 ? 6 : 5) : (WAVES >= 8 ? 8 : 7); }
 
-template <int WAVES, int S, int ROUNDS>
+template <int WAVES, int S, int ROUNDS, int CL = 64>
 __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void sketch_wave_kernel(Sketch2Args B)
 {
-    constexpr int C = 64;
+    constexpr int C = CL;                              /* k-mers per lane: strips of 64 C = 4096 or 8192 ordinals (WindowPlan::nt = 4 C lanes of 16 to the other passes) */
+    constexpr uint32_t TAGM = (uint32_t)C - 1u;        /* the low bits of a staged key that hold its step */
+    constexpr uint32_t NEAR = skw_near<C>();
+    static_assert(C == 64 || C == 128, "a lane's bases are five or nine words on either side");
+    static_assert(ROUNDS <= 32, "`found` has a bit per scan round");
+    static_assert(64 * C <= 0xFFFF && 64u * ROUNDS <= 0xFFFFu, "StripLite::hi and the scanners' indices are 16 bits");
     constexpr uint32_t SLOTS = 64u * (uint32_t)S;      /* words of a wavefront's key array: staging slots, then the list's keys in place */
     constexpr uint32_t NLIST = 64u * (uint32_t)ROUNDS; /* list entries: [3] left sentinel, [4 .. n + 3] candidates, [n + 4] right sentinel, copies around them */
     constexpr uint32_t CAP = NLIST - 8u;               /* candidates the list holds */
@@ -1042,8 +1113,14 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
         const uint32_t Cs = ntl_readfirstlane(skw_per_lane(hi_raw)); /* k-mers per lane of this strip */
         const uint32_t lane_pos = (uint32_t)L * Cs;
         const uint32_t tm1 = lane_pos < hi ? B.thresh - 1u : 0u; /* lanes behind the sequence's last k-mer roll over whatever follows it: nothing of theirs is a candidate */
-        uint32_t low6 = 63u;
-        NTL_OPAQUE(low6); /* a register, not a literal per step; and not loop-invariant for the optimiser */
+        uint32_t tagm = TAGM;
+        NTL_OPAQUE(tagm); /* a register, not a literal per step; and not loop-invariant for the optimiser */
+        /* (8192-ordinal strips) the words of the lane's second 64 k-mers: asked for here, used behind the first 64 steps */
+        SkwWords2 H;
+        if constexpr (C > 64) {
+            H.o5 = H.i5 = make_uint4(0u, 0u, 0u, 0u);
+            if (Cs > 64u) H = skw_words2_load(A.T.packed, Ic, L, k, wmax);
+        }
 
         /* ---- the first k-mer's rings from the lane's own bases: 16-base partial hashes out of the four-base tables ---- */
         uint32_t fx, ry;
@@ -1082,37 +1159,16 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
         uint32_t *dst = slots;
         {
             uint32_t fd = fx << 1;
-            if (fd + ry <= tm1) ntl_lds_push_tagged<0>(dst, low6, fd + ry);
+            if (fd + ry <= tm1) ntl_lds_push_tagged<0>(dst, tagm, fd + ry);
 #pragma unroll
-            for (int m = 0; m < 4; m++) {
-                if ((uint32_t)(16 * m) >= Cs) break; /* (a short last strip: its lanes hold 16, 32 or 48 k-mers; the step that a block of
+            for (int m = 0; m < C / 16; m++) {
+                if ((uint32_t)(16 * m) >= Cs) break; /* (a short last strip: its lanes hold 16, 32, ... k-mers; the step that a block of
                                                         sixteen makes beyond them is the next lane's first k-mer, dropped below) */
-                uint32_t wz[4];
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const uint32_t o2 = r < 2 ? so[m] << (3 - 2 * r) : so[m] >> (2 * r - 3);
-                    const uint32_t i2 = r < 3 ? si[m] << (5 - 2 * r) : si[m] >> (2 * r - 5);
-                    wz[r] = (o2 & 0x18181818u) | (i2 & 0x60606060u);
+                if (C > 64 && m == 4) { /* the second 64 k-mers' bases take the place of the first 64's */
+                    so[0] = ntl_alignbit(H.o5.x, Wc.o4, Wc.ao); so[1] = ntl_alignbit(H.o5.y, H.o5.x, Wc.ao); so[2] = ntl_alignbit(H.o5.z, H.o5.y, Wc.ao); so[3] = ntl_alignbit(H.o5.w, H.o5.z, Wc.ao);
+                    si[0] = ntl_alignbit(H.i5.x, Wc.i4, Wc.ai); si[1] = ntl_alignbit(H.i5.y, H.i5.x, Wc.ai); si[2] = ntl_alignbit(H.i5.z, H.i5.y, Wc.ai); si[3] = ntl_alignbit(H.i5.w, H.i5.z, Wc.ai);
                 }
-                /* the seed pairs of eight steps are requested together, in front of the steps: every step ends in a predicated
-                   write (a basic block of its own), and a read issued inside a step would be waited for inside it */
-#pragma unroll
-                for (int h = 0; h < 2; h++) {
-                    uint2 sd[8];
-#pragma unroll
-                    for (int b = 8 * h; b < 8 * h + 8; b++) {
-                        const uint32_t off = ntl_bfe(wz[b & 3], 8u * (uint32_t)(b >> 2), 8u);
-                        sd[b & 7] = ntl_lds_load2_ordered((const uint2 *)((const char *)s_roll + off));
-                    }
-                    if (m == 0 && h == 0) skw_steps<1>(std::make_integer_sequence<int, 8>(), fx, ry, fd, sd, tm1, low6, dst);
-                    else if (m == 0) skw_steps<9>(std::make_integer_sequence<int, 8>(), fx, ry, fd, sd, tm1, low6, dst);
-                    else if (m == 1 && h == 0) skw_steps<17>(std::make_integer_sequence<int, 8>(), fx, ry, fd, sd, tm1, low6, dst);
-                    else if (m == 1) skw_steps<25>(std::make_integer_sequence<int, 8>(), fx, ry, fd, sd, tm1, low6, dst);
-                    else if (m == 2 && h == 0) skw_steps<33>(std::make_integer_sequence<int, 8>(), fx, ry, fd, sd, tm1, low6, dst);
-                    else if (m == 2) skw_steps<41>(std::make_integer_sequence<int, 8>(), fx, ry, fd, sd, tm1, low6, dst);
-                    else if (h == 0) skw_steps<49>(std::make_integer_sequence<int, 8>(), fx, ry, fd, sd, tm1, low6, dst);
-                    else skw_steps<57>(std::make_integer_sequence<int, 7>(), fx, ry, fd, sd, tm1, low6, dst);
-                }
+                skw_block_at<C>(std::make_integer_sequence<int, C / 16>(), m, so[m & 3], si[m & 3], s_roll, fx, ry, fd, tm1, tagm, dst);
             }
         }
         /* the next strip's base words: asked for HERE, behind the rolling loop (where the registers are scarcest: twelve of them held
@@ -1128,13 +1184,13 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
 #pragma unroll
         for (int j = 0; j < S; j++) mine[j] = (uint32_t)j < cnt ? slots[j] : SK2_INF;
         uint32_t first = 0, k0 = SK2_INF;
-        if (L == 0 && cnt && (mine[0] & 63u) == 0u) { first = 1; cnt--; k0 = mine[0]; } /* element 0 belongs to the windows of the previous strip only */
+        if (L == 0 && cnt && (mine[0] & TAGM) == 0u) { first = 1; cnt--; k0 = mine[0]; } /* element 0 belongs to the windows of the previous strip only */
         k0 = ntl_readfirstlane(k0);
         if (hi < (uint32_t)(64 * C)) { /* the sequence ends inside the strip: positions >= hi are not elements (nor is a lane's step Cs) */
             uint32_t keep = 0;
 #pragma unroll
             for (int j = 0; j < S; j++)
-                if ((uint32_t)j >= first && (uint32_t)j < first + cnt && (mine[j] & 63u) < Cs && lane_pos + (mine[j] & 63u) < hi) keep++;
+                if ((uint32_t)j >= first && (uint32_t)j < first + cnt && (mine[j] & TAGM) < Cs && lane_pos + (mine[j] & TAGM) < hi) keep++;
             cnt = keep;
         }
         const uint32_t incl = ntl_wave_incl_scan(cnt);
@@ -1148,7 +1204,7 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
             for (int j = 0; j < S; j++)
                 if ((uint32_t)j >= first && (uint32_t)j < first + cnt) {
                     keys[at + (uint32_t)j] = mine[j];
-                    pos[at + (uint32_t)j] = lane_pos + (mine[j] & 63u);
+                    pos[at + (uint32_t)j] = lane_pos + (mine[j] & TAGM);
                 }
         }
         if (L < 4) {
@@ -1158,7 +1214,7 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
         ntl_wave_sync();
 
         /* ---- round 6: who has to scan at all.  Four candidates in five are nobody's minimum, and most of them show it at once: a
-           candidate with a CERTAINLY smaller key (more than SKW_NEAR below its own: the keys then order the hashes) among its four
+           candidate with a CERTAINLY smaller key (more than NEAR below its own: the keys then order the hashes) among its four
            list neighbours on either side, all eight of them less than a window apart, lies in no window without one of the two --
            whatever else the strip holds, whatever the keys above the threshold are, however its ties fall.  One pass over the
            list, a lane per candidate, a dozen LDS reads and no loop, takes those out (71 % of them: P(the least of five on one side)
@@ -1186,12 +1242,12 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
                 const bool inw0 = real && mp < w;
                 uint32_t kmin = ntl_wave_min(inw0 ? mk : SK2_INF);
                 kmin = kmin < k0 ? kmin : k0;
-                const bool near0 = inw0 && mk <= kmin + SKW_NEAR;
-                const uint32_t nn = (uint32_t)__popcll(__ballot(near0)) + (k0 != SK2_INF && k0 <= kmin + SKW_NEAR ? 1u : 0u);
+                const bool near0 = inw0 && mk <= kmin + NEAR;
+                const uint32_t nn = (uint32_t)__popcll(__ballot(near0)) + (k0 != SK2_INF && k0 <= kmin + NEAR ? 1u : 0u);
                 b |= nn != 1u || kmin == SK2_INF || (n > 64u && pos[67] < w); /* a near tie, no candidate, or more than this round sees */
                 scan = scan && !near0;
             }
-            const uint32_t sure = ntl_sub_sat(mk, SKW_NEAR); /* keys below it are certainly smaller (none, for a key within the tolerance of the sentinels' 0) */
+            const uint32_t sure = ntl_sub_sat(mk, NEAR); /* keys below it are certainly smaller (none, for a key within the tolerance of the sentinels' 0) */
             /* how far apart the two are: the second neighbour's position where one of the nearer two is smaller, else the fourth's (the nearer
                smaller one's own position would be a read more and decide 2 candidates of 164 more; the fourth's alone, 22 fewer) */
             const uint32_t ml2 = l0 < l1 ? l0 : l1, mr2 = r0 < r1 ? r0 : r1;
@@ -1219,7 +1275,7 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
             const bool real = j0 < ns;
             const uint32_t i = sidx[real ? j0 : ns - 1u];
             const uint32_t mk = keys[i + 4u], mp = pos[i + 4u];
-            const uint32_t lim = mk + SKW_NEAR;
+            const uint32_t lim = mk + NEAR;
             bool b = lim >= B.thresh;
             uint32_t Rp = mp + w < V ? mp + w : V;
             uint32_t q0, q1, q2, q3;
@@ -1236,7 +1292,7 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
                 const uint32_t *ke = kp + (fb != 4u ? fb : 3u);
                 const uint32_t ek = ke[0], ep = ke[KP];
                 const bool take = fb != 4u && ep < Rp;
-                b |= take && ek + SKW_NEAR >= mk; /* within the tolerance of the candidate's own key (the sentinel's key 0: only for keys <= SKW_NEAR) */
+                b |= take && ek + NEAR >= mk; /* within the tolerance of the candidate's own key (the sentinel's key 0: only for keys <= NEAR) */
                 Rp = take ? ep : Rp;
             }
             const int32_t need = (int32_t)Rp - (int32_t)w; /* a blocker at q < pos matters where q >= need */
@@ -1256,7 +1312,7 @@ __global__ __launch_bounds__(64 * WAVES, (skw_waves_per_simd<WAVES, S>())) void 
                 blocked = fb != 4u && (int32_t)ke[KP] >= need;
                 /* ... and is it certainly smaller?  (Round 6.  While every candidate scanned, a near tie of two candidates was seen from
                    its left one, whose scan to the right ends at the other; now the left one may have dropped out before the scans.) */
-                b |= blocked && ek + SKW_NEAR >= mk;
+                b |= blocked && ek + NEAR >= mk;
             }
             if (real) {
                 bad |= b;

@@ -19,10 +19,12 @@
  *   94 <= w <= 1135, k <= 64           sketch_wave_kernel + sketch_fast_list_kernel<256, R0, w > 255>, strip lists (WAVE):
  *       94 <= w <= 136                     <4, 19, 8> beside the other stream's kernels, <8, 19, 8> alone
  *       137 <= w <= 234                    <8, 15, 6>
- *       235 <= w <= 1135                   <8, 11, 4>
+ *       235 <= w <= 1135                   <8, 11, 4>  (by knob, NTL_SKETCH_STRIP=8192: <8, 19, 7, 128> on strips of 8192 ordinals)
  *
- * Every 32-bit pass is followed by the exact pass over the strips it flagged.  The w boundaries above 70 are those of the candidates a
- * strip of 4096 k-mers is expected to hold, 4096 T / 2^32 = 40960 / w at the default ten candidates per window, against:
+ * Every 32-bit pass is followed by the exact pass over the strips it flagged.  A sketch has one strip length, nt lanes of 16 k-mers:
+ * 4096 ordinals (2048 for w < 64) unless that knob is set, and every pass behind the wave kernel is instantiated for it
+ * (sketch_fast_list_kernel<512, ..>, sketch_mask_kernel<16, 512, ..>).  The w boundaries above 70 are those of the candidates
+ * 4096 k-mers are expected to hold, 4096 T / 2^32 = 40960 / w at the default ten candidates per window, against:
  */
 static const double WP_FIT_THRESH = 580.0; /* above: no threshold (sketch_thresh_kernel<.., DIRECT>'s list of 680 with room for the spread) */
 static const double WP_FIT_WAVE = 440.0;   /* above: not sketch_wave_kernel (its largest shape's list: 8 rounds of 64) */
@@ -31,13 +33,15 @@ static const double WP_FIT_15_6 = 300.0;   /* above: the <.., 19, 8> shapes, and
 static const double WP_FIT_11_4 = 175.0;   /* above: <8, 15, 6> */
 
 enum WindowPass { WP_SMALL, WP_EXACT_ONLY, /* the 32-bit passes, each with the exact pass over what it flags: */ WP_BLOCK_MINIMA, WP_THRESH, WP_WAVE };
-/* sketch_wave_kernel<wavefronts per workgroup, staging slots per lane, scan rounds>: the slots hold a lane's 64 p candidates + 4.5 sigma,
-   the list (64 per round) a strip's 4096 p + 4 sigma; what does not fit is given up.  The first WS_DEFAULTS are some (k, w)'s default */
-enum WaveShape { WS_8_11_4, WS_8_15_6, WS_8_19_8, WS_4_19_8, WS_DEFAULTS, WS_4_11_4 = WS_DEFAULTS, WS_16_11_4 };
+/* sketch_wave_kernel<wavefronts per workgroup, staging slots per lane, scan rounds, k-mers per lane = 64>: the slots hold a lane's 64 p
+   candidates + 4.5 sigma, the list (64 per round) a strip's 4096 p + 4 sigma; what does not fit is given up.  <8, 19, 7, 128>: a lane
+   stages 5.12 candidates on average at w = 250 and P(Poisson(5.12) > 19) = 5 10^-7, a strip in 3 10^-5 is given up for it (17 slots:
+   5 10^-4; the 4096 shape's eleven: 10^-3); the list holds 440 for a mean of 328 (sigma 18).  The first WS_DEFAULTS are some (k, w)'s default */
+enum WaveShape { WS_8_11_4, WS_8_15_6, WS_8_19_8, WS_4_19_8, WS_8_19_7_L128, WS_DEFAULTS, WS_4_11_4 = WS_DEFAULTS, WS_16_11_4 };
 
 struct WindowPlan {
     SketchGeom G;
-    int C, nt;             /* k-mers per lane, lanes per strip */
+    int C, nt;             /* k-mers per lane, lanes per strip (of the workgroup-per-strip passes: sketch_wave_kernel's lane holds nt / 4 k-mers) */
     uint64_t strips;       /* upper bound from the host-side lengths (exact for sequences without non-ACGT bytes): grids are sized without waiting for the device */
     WindowPass pass;
     bool big, direct;      /* BLOCK_MINIMA and the list pass behind WAVE: the kernel's BIG form; THRESH: the variant without staged keys */
@@ -47,7 +51,7 @@ struct WindowPlan {
     uint32_t chunk_budget; /* WAVE: NTL_SKW_BUDGET (0: resident wavefronts; tuning, tools/share_sweep.py) */
     uint32_t thresh;       /* keys below it are candidates; 0: no threshold */
     int dbg, force_redo;
-    double expected_per_strip; /* candidates a strip is expected to hold */
+    double expected_per_strip; /* candidates 4096 k-mers are expected to hold */
     bool dense_windows;    /* for the emit grid */
     bool lists;            /* the passes write per-strip lists of minimizers, not the bitmask */
     uint32_t slot, pool;   /* entries of a strip's list slot / of the pool behind the slots */
@@ -62,6 +66,7 @@ static void with_wave_kernel(WaveShape shape, F &&f)
     case WS_8_15_6: return f(sketch_wave_kernel<8, 15, 6>, 512u);
     case WS_8_19_8: return f(sketch_wave_kernel<8, 19, 8>, 512u);
     case WS_4_19_8: return f(sketch_wave_kernel<4, 19, 8>, 256u);
+    case WS_8_19_7_L128: return f(sketch_wave_kernel<8, 19, 7, 128>, 512u);
     case WS_4_11_4: return f(sketch_wave_kernel<4, 11, 4>, 256u);
     case WS_16_11_4: return f(sketch_wave_kernel<16, 11, 4>, 1024u);
     }
