@@ -207,10 +207,25 @@ uint64_t ntl_sketch_redo_strips(const ntl_sketch *s);
 /* ... and how many strips the threshold pass (71 <= w <= 255: only k-mers with a small key are looked at) handed to the
  * block-minima pass because one of their windows had no such k-mer (about 0.7 % on random sequence). */
 uint64_t ntl_sketch_fallback_strips(const ntl_sketch *s);
-/* ... and whether the window passes wrote per-strip minimizer LISTS (1: the windows ntLink runs with, 94 <= w <= 255, k <= 64) or
+/* ... and whether the window passes wrote per-strip minimizer LISTS (1: the windows ntLink runs with, 94 <= w <= 1151, k <= 64) or
  * the bitmask of one bit per base (0: every other window; NTL_SKETCH_LISTS=0; a sketch whose lists ran out of room -- low-complexity
  * sequence throughout -- and was made again).  The result is the same either way. */
 int ntl_sketch_from_lists(const ntl_sketch *s);
+/* ... and the plan of the window pass that the last round of the sketch carried out, as decided for its (k, w), the number of
+ * streams and the tuning knobs -- which kernel ran, on which strips (diagnostics and tests; the result is the same whatever it says).
+ * pass: NTL_PASS_*; nt lanes of C k-mers make a strip, which owns NWO windows; big: the two-level form of the block-minima pass (of the
+ * list pass behind the wave kernel); direct: the threshold pass without staged keys; wave_*: the four template numbers of
+ * sketch_wave_kernel (0 for every other pass); lists as ntl_sketch_from_lists; thresh: keys below it are candidates (0: none). */
+enum { NTL_PASS_SMALL = 0, NTL_PASS_EXACT_ONLY = 1, NTL_PASS_BLOCK_MINIMA = 2, NTL_PASS_THRESH = 3, NTL_PASS_WAVE = 4 };
+typedef struct ntl_plan_info {
+    int32_t pass;
+    int32_t nt, C, NWO;
+    int32_t big, direct;
+    int32_t wave_wavefronts, wave_slots, wave_rounds, wave_kmers; /* wavefronts per workgroup, slots per lane, scan rounds, k-mers per lane */
+    int32_t lists;
+    uint32_t thresh;
+} ntl_plan_info;
+int ntl_sketch_plan(const ntl_sketch *s, ntl_plan_info *out);
 /* mx_off[nseq+1]: minimizers of sequence i are [mx_off[i], mx_off[i+1]); hash/pos/strand hold
  * ntl_sketch_count() entries (the three fields `indexlr` prints as H:pos:strand). */
 int ntl_sketch_download(const ntl_sketch *s, uint64_t *mx_off, uint64_t *hash, uint32_t *pos,

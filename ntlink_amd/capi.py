@@ -22,7 +22,7 @@ SYMBOLS = [
     "ntl_batch_create", "ntl_batch_create_packed", "ntl_batch_create_packed_at", "ntl_packed_words", "ntl_batch_destroy", "ntl_batch_nseq", "ntl_batch_bases", "ntl_host_alloc", "ntl_host_free",
     "ntl_synth_genome", "ntl_synth_slices", "ntl_batch_download",
     "ntl_sketch_run", "ntl_sketch_run_indexed", "ntl_sketch_run_for_map", "ntl_sketch_has_records", "ntl_sketch_destroy", "ntl_sketch_nseq", "ntl_sketch_count", "ntl_sketch_download",
-    "ntl_sketch_strips", "ntl_sketch_redo_strips", "ntl_sketch_fallback_strips", "ntl_sketch_from_lists", "ntl_sketch_wait", "ntl_mapres_wait",
+    "ntl_sketch_strips", "ntl_sketch_redo_strips", "ntl_sketch_fallback_strips", "ntl_sketch_from_lists", "ntl_sketch_plan", "ntl_sketch_wait", "ntl_mapres_wait",
     "ntl_sketch_from_host", "ntl_overlap_filter",
     "ntl_index_build", "ntl_index_destroy", "ntl_index_size",
     "ntl_map_run", "ntl_mapres_destroy", "ntl_mapres_n_mappings", "ntl_mapres_n_hits", "ntl_mapres_n_pafs",
@@ -47,6 +47,14 @@ class MapParams(C.Structure):
     _fields_ = [("k", C.c_int32), ("z", C.c_int32), ("x", C.c_double),
                 ("sensitive", C.c_int32), ("repeat_filter", C.c_int32)]
 
+
+class PlanInfo(C.Structure):
+    """ntl_plan_info"""
+    _fields_ = [(nm, C.c_int32) for nm in ("pass", "nt", "C", "NWO", "big", "direct", "wave_wavefronts", "wave_slots", "wave_rounds",
+                                           "wave_kmers", "lists")] + [("thresh", C.c_uint32)]
+
+
+PASSES = ("small", "exact_only", "block_minima", "thresh", "wave")  # NTL_PASS_*
 
 NTL_EINVAL, NTL_EDEVICE, NTL_ENOMEM, NTL_EINTERNAL, NTL_ERANGE = -1, -2, -3, -4, -5
 
@@ -120,6 +128,7 @@ def load(path=None):
         getattr(L, nm).argtypes = [vp]
         getattr(L, nm).restype = C.c_uint64
     L.ntl_sketch_from_lists.argtypes = [vp]
+    L.ntl_sketch_plan.argtypes = [vp, C.POINTER(PlanInfo)]
     L.ntl_sketch_download.argtypes = [vp, u64p, u64p, u32p, u8p]
     L.ntl_sketch_from_host.argtypes = [vp, C.c_uint64, u64p, u64p, u32p, u8p, C.POINTER(vp)]
     L.ntl_overlap_filter.argtypes = [vp, vp, u64p, u32p, u32p, C.POINTER(vp)]
@@ -289,6 +298,18 @@ class Sketch(_Handle):
         """True: the window passes wrote per-strip minimizer lists; False: the bitmask (diagnostics; same result)."""
         self.wait()
         return bool(self.dev.L.ntl_sketch_from_lists(self.ptr))
+
+    @property
+    def plan(self):
+        """The window pass the sketch ran (ntl_sketch_plan; diagnostics): dict(pass= one of PASSES, nt=, C=, NWO=, big=, direct=,
+        shape= sketch_wave_kernel's (wavefronts per workgroup, slots per lane, scan rounds, k-mers per lane) or None, lists=, thresh=)."""
+        info = PlanInfo()
+        self.dev._chk(self.dev.L.ntl_sketch_plan(self.ptr, C.byref(info)))
+        wave = PASSES[getattr(info, "pass")] == "wave"
+        return {"pass": PASSES[getattr(info, "pass")], "nt": info.nt, "C": info.C, "NWO": info.NWO, "big": bool(info.big),
+                "direct": bool(info.direct),
+                "shape": (info.wave_wavefronts, info.wave_slots, info.wave_rounds, info.wave_kmers) if wave else None,
+                "lists": bool(info.lists), "thresh": info.thresh}
 
     def download(self):
         """(mx_off u64[nseq+1], hash u64, pos u32, strand u8 [1 = '+'])."""

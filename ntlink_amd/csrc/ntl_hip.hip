@@ -1286,6 +1286,7 @@ struct ntl_sketch {
     mutable DevBuf cand;    /* Cand[cap] */
     bool no_records = false; /* ntl_sketch_run_for_map: `records` stays empty */
     mutable bool from_lists = false; /* diagnostics: the last round of sketch_enqueue wrote lists */
+    mutable ntl_plan_info plan = {};  /* diagnostics: the WindowPlan the last round of sketch_enqueue carried out (ntl_sketch_plan) */
     mutable bool no_lists = false; /* the window stage writes the bitmask whatever the window: the second round of a sketch whose lists ran out of pool */
     mutable DevBuf rpos;    /* u32[cap] beside cand: the minimizers' positions in their reads (their strands: bit 31 of Cand::meta) */
     mutable DevBuf sums;    /* SketchSums on the device: total (read by the map kernels: a sketch that overflowed its arrays is left alone) */
@@ -1610,7 +1611,7 @@ static int window_plan(ntl_ctx *c, const ntl_batch *b, int k, int w, bool no_lis
     P.dense_windows = P.expected_per_strip > WP_FIT_15_6;
     const bool sparse = P.thresh && (P.dbg & ~24) == 0; /* (ablation bits 8 and 16 exist in the threshold and wave kernels too) */
     /* one wavefront per strip, 64 k-mers per lane (sketch_wave_kernel) where a lane's first k-mer lies in its own 64 bases and a strip's
-       candidates fit its list: a window only enters its scans as a distance, so it goes up to the block-minima pass's w <= 1135, which
+       candidates fit its list: a window only enters its scans as a distance, so it goes up to the block-minima pass's w <= 1151, which
        decides the strips it gives up.  NTL_SKETCH_WAVE=0: the workgroup-per-strip forms; 4, 8, 16: wavefronts per workgroup (A/B, tests) */
     const char *we = getenv("NTL_SKETCH_WAVE");
     const int wave = we ? atoi(we) : 1;
@@ -2018,6 +2019,13 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     }
     s->strips = ub_strips;
     s->from_lists = lists;
+    {   /* the plan that was carried out, as plain integers (ntl_sketch_plan) */
+        ntl_plan_info &I = s->plan;
+        memset(&I, 0, sizeof I);
+        I.pass = (int32_t)P.pass; I.nt = P.nt; I.C = P.C; I.NWO = G.NWO;
+        I.big = P.big; I.direct = P.direct; I.lists = P.lists; I.thresh = P.thresh;
+        if (P.pass == WP_WAVE) wave_shape_numbers(P.shape, &I.wave_wavefronts);
+    }
     s->pending = true;
     /* temporaries return to the context's cache here; every later user of those blocks is queued behind the kernels above
        on the stream they were used on, so no wait is needed */
@@ -2131,6 +2139,15 @@ extern "C" uint64_t ntl_sketch_strips(const ntl_sketch *s) { return s ? s->strip
 extern "C" uint64_t ntl_sketch_redo_strips(const ntl_sketch *s) { return s && sketch_finalize(s) == NTL_OK ? s->redo_strips : 0; }
 extern "C" int ntl_sketch_from_lists(const ntl_sketch *s) { return s && sketch_finalize(s) == NTL_OK && s->from_lists ? 1 : 0; }
 extern "C" uint64_t ntl_sketch_fallback_strips(const ntl_sketch *s) { return s && sketch_finalize(s) == NTL_OK ? s->fallback_strips : 0; }
+static_assert(WP_SMALL == NTL_PASS_SMALL && WP_EXACT_ONLY == NTL_PASS_EXACT_ONLY && WP_BLOCK_MINIMA == NTL_PASS_BLOCK_MINIMA &&
+              WP_THRESH == NTL_PASS_THRESH && WP_WAVE == NTL_PASS_WAVE, "WindowPass is ntl_plan_info's `pass`");
+extern "C" int ntl_sketch_plan(const ntl_sketch *s, ntl_plan_info *out)
+{
+    if (!s || !out) return NTL_EINVAL;
+    const int rc = sketch_finalize(s); /* (a sketch that overflowed is made again there: the plan is the last round's) */
+    if (rc == NTL_OK) *out = s->plan;
+    return rc;
+}
 
 extern "C" int ntl_sketch_download(const ntl_sketch *s, uint64_t *mx_off, uint64_t *hash, uint32_t *pos, uint8_t *strand)
 {

@@ -48,7 +48,7 @@
 
 #define SK2_JOBCAP 512 /* searched windows per strip; more (pathological sequence) hands the strip to the exact pass */
 #define SK2_QMAX 16     /* k <= 16 * SK2_QMAX */
-#define SK2_PAD 72      /* whole blocks right of a window's first block: a + 2 <= SK2_PAD, i.e. w <= 1135; larger windows take the exact pass */
+#define SK2_PAD 72      /* whole blocks right of a window's first block: a + 2 <= SK2_PAD, a = (w - 16) / 16, i.e. w <= 1151; larger windows take the exact pass */
 #define SK2_INF 0xFFFFFFFFu
 #define SK2_NEAR 3u     /* keys closer than this + 1 do not order their k-mers (see "exact") */
 /* phase ablation for tools/gpu_ablate.sh (results WRONG): only in builds with -DNTL_SKETCH_ABLATION, so that the product
@@ -165,7 +165,7 @@ __device__ __forceinline__ void sk2_fast_strip(const Sketch2Args &B, const uint3
     constexpr int NX = NT + SK2_QMAX + 1;
     /* BIG = false (a + 2 <= 16, i.e. w <= 255: the windows ntLink runs with): one range-minimum level, a short job list in the
        bytes of the rolling table (dead after phase 1), 16 INF entries -> 20.4 KB: EIGHT workgroups (32 wavefronts) per CU.
-       BIG = true (w <= 1135): two levels, 72 INF entries, 512 jobs -> 23.2 KB, seven workgroups. */
+       BIG = true (w <= 1151): two or three levels, 72 INF entries, 512 jobs -> 23.2 KB, seven workgroups. */
     constexpr int PAD = BIG ? SK2_PAD : 16;     /* INF entries behind the block minima: a + 2 <= PAD (ntl_sketch_run checks) */
     constexpr int JOBCAP = BIG ? SK2_JOBCAP : 128;
     /* s_c doubles as the exchange area of phase 1:
@@ -525,7 +525,7 @@ __global__ __launch_bounds__(NT) void sketch_fast_list_kernel(Sketch2Args B, con
 {
     const uint32_t n = *count;
     for (uint32_t i = blockIdx.x; i < n; i += gridDim.x) {
-        sk2_fast_strip<NT, R0, BIG>(B, list[i]); /* (BIG: windows of 256 .. 1135 k-mers, which sketch_wave_kernel takes since round 6) */
+        sk2_fast_strip<NT, R0, BIG>(B, list[i]); /* (BIG: windows of 256 .. 1151 k-mers, which sketch_wave_kernel takes since round 6) */
         __syncthreads(); /* the next strip's first writes to LDS behind this one's last reads */
     }
 }
@@ -879,7 +879,7 @@ __global__ __launch_bounds__(NT) void sketch_thresh_kernel(Sketch2Args B)
  * and positions >= hi = min(64 CL, M - E0) lie behind the sequence: candidates found there are dropped when the list is made.
  * Gives the strip up (B.fb_list) when a lane stages more than S candidates, the list would hold more than 64 ROUNDS - 8, or the
  * scans say so (a window without a candidate, a near tie, a key within skw_near of the threshold).  Round 6: one pass over the list
- * decides which candidates scan at all (below: "who has to scan"), and the window may be anything up to the block-minima pass's 1135
+ * decides which candidates scan at all (below: "who has to scan"), and the window may be anything up to the block-minima pass's 1151
  * k-mers -- it only enters the scans as a distance (the workgroup-per-strip passes' a + 2 <= 16 lanes is not this kernel's limit).
  * Soaked against the oracle on
  * 24 Gbases and 985 random (k, w, candidates per window) configurations (profiles/r04s_*.log), and in every `pytest -m gpu` run

@@ -8,19 +8,23 @@
 /*
  * Which window pass a sketch runs with no knob set (DESIGN.md 4.1 holds the same table):
  *
- *   w = 1; k > 256; w > 1135           sketch_mask_kernel<1 / 16> alone (EXACT_ONLY; <4> and <1> for 2 <= w <= 15 only by knob)
- *   2 <= w <= 15                       sketch_small_kernel<W>                                                     (SMALL)
- *   16 <= w < 64                       sketch_fast_kernel<128, R0, true>                                          (BLOCK_MINIMA)
+ *   2 <= w <= 15, any k                sketch_small_kernel<W>                                                     (SMALL)
+ *   w = 1; w > 1151 (w <= 4063);
+ *   k > 256 (w = 1 or w >= 16)         sketch_mask_kernel<1 / 16> alone (EXACT_ONLY; <4> and <1> for 2 <= w <= 15 only by knob)
+ *   below, k <= 256:
+ *   16 <= w < 64                       sketch_fast_kernel<128, R0, true>                                          (BLOCK_MINIMA, big)
  *   64 <= w <= 70                      sketch_fast_kernel<256, R0, false>                                         (BLOCK_MINIMA)
  *   71 <= w <= 93, and
  *   94 <= w <= 120 when k > 64         sketch_thresh_kernel<256, true> + sketch_fast_list_kernel<256, R0>         (THRESH, direct)
  *   121 <= w <= 255 when k > 64        sketch_thresh_kernel<256, false> + sketch_fast_list_kernel<256, R0>        (THRESH)
- *   256 <= w <= 1135 when k > 64       sketch_fast_kernel<256, R0, true>                                          (BLOCK_MINIMA)
- *   94 <= w <= 1135, k <= 64           sketch_wave_kernel + sketch_fast_list_kernel<256, R0, w > 255>, strip lists (WAVE):
+ *   256 <= w <= 1151 when k > 64       sketch_fast_kernel<256, R0, true>                                          (BLOCK_MINIMA, big)
+ *   94 <= w <= 1151, k <= 64           sketch_wave_kernel + sketch_fast_list_kernel<256, R0, w > 255>, strip lists (WAVE; big: w > 255):
  *       94 <= w <= 136                     <4, 19, 8> beside the other stream's kernels, <8, 19, 8> alone
  *       137 <= w <= 234                    <8, 15, 6>
- *       235 <= w <= 1135                   <8, 11, 4>  (by knob, NTL_SKETCH_STRIP=8192: <8, 19, 7, 128> on strips of 8192 ordinals)
+ *       235 <= w <= 1151                   <8, 11, 4>  (by knob, NTL_SKETCH_STRIP=8192: <8, 19, 7, 128> on strips of 8192 ordinals)
  *
+ * (w <= 1151: a + 2 <= SK2_PAD blocks right of a window's first, a = (w - 16) / 16.)  tests/test_window_plan.py states the same table
+ * a third time, reads it back from sketches (ntl_sketch_plan) on both sides of every boundary, and must change with it.
  * Every 32-bit pass is followed by the exact pass over the strips it flagged.  A sketch has one strip length, nt lanes of 16 k-mers:
  * 4096 ordinals (2048 for w < 64) unless that knob is set, and every pass behind the wave kernel is instantiated for it
  * (sketch_fast_list_kernel<512, ..>, sketch_mask_kernel<16, 512, ..>).  The w boundaries above 70 are those of the candidates
@@ -58,16 +62,28 @@ struct WindowPlan {
     bool fast() const { return pass >= WP_BLOCK_MINIMA; }
 };
 
+/* the shapes sketch_wave_kernel is instantiated for, once: the launch (with_wave_kernel) and the diagnostics (wave_shape_numbers,
+   ntl_sketch_plan) read the same four template numbers */
+#define NTL_WAVE_SHAPES(X) \
+    X(WS_8_11_4, 8, 11, 4, 64) X(WS_8_15_6, 8, 15, 6, 64) X(WS_8_19_8, 8, 19, 8, 64) X(WS_4_19_8, 4, 19, 8, 64) \
+    X(WS_8_19_7_L128, 8, 19, 7, 128) X(WS_4_11_4, 4, 11, 4, 64) X(WS_16_11_4, 16, 11, 4, 64)
+
 template <typename F>
 static void with_wave_kernel(WaveShape shape, F &&f)
 {
     switch (shape) {
-    case WS_8_11_4: return f(sketch_wave_kernel<8, 11, 4>, 512u);
-    case WS_8_15_6: return f(sketch_wave_kernel<8, 15, 6>, 512u);
-    case WS_8_19_8: return f(sketch_wave_kernel<8, 19, 8>, 512u);
-    case WS_4_19_8: return f(sketch_wave_kernel<4, 19, 8>, 256u);
-    case WS_8_19_7_L128: return f(sketch_wave_kernel<8, 19, 7, 128>, 512u);
-    case WS_4_11_4: return f(sketch_wave_kernel<4, 11, 4>, 256u);
-    case WS_16_11_4: return f(sketch_wave_kernel<16, 11, 4>, 1024u);
+#define NTL_WAVE_CASE(id, waves, slots, rounds, cl) case id: return f(sketch_wave_kernel<waves, slots, rounds, cl>, 64u * waves);
+    NTL_WAVE_SHAPES(NTL_WAVE_CASE)
+#undef NTL_WAVE_CASE
+    }
+}
+
+/* {wavefronts per workgroup, staging slots per lane, scan rounds, k-mers per lane} of a shape */
+static void wave_shape_numbers(WaveShape shape, int32_t out[4])
+{
+    switch (shape) {
+#define NTL_WAVE_CASE(id, waves, slots, rounds, cl) case id: out[0] = waves; out[1] = slots; out[2] = rounds; out[3] = cl; return;
+    NTL_WAVE_SHAPES(NTL_WAVE_CASE)
+#undef NTL_WAVE_CASE
     }
 }

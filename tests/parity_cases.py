@@ -15,18 +15,58 @@ def offsets_of(seqs):
     return off
 
 
-def check_sketch(dev, seqs, k, w, threads=0, info=None):
-    """Device sketch == oracle sketch (offsets, hashes, positions, strands).  info (dict): strips / redo_strips of the run."""
-    with dev.batch(seqs) as b, dev.sketch(b, k, w) as sk:
-        off, h, p, s = sk.download()
-        if info is not None:
-            info.update(strips=sk.strips, redo_strips=sk.redo_strips, fallback_strips=sk.fallback_strips, from_lists=sk.from_lists)
+def verify_sketch(sk, seqs, k, w, threads=0, info=None):
+    """A queued sketch of seqs == the oracle's (offsets, hashes, positions, strands).  info (dict): strips / redo_strips / plan of the run."""
+    off, h, p, s = sk.download()
+    if info is not None:
+        info.update(strips=sk.strips, redo_strips=sk.redo_strips, fallback_strips=sk.fallback_strips, from_lists=sk.from_lists,
+                    plan=sk.plan)
     ooff, oh, op, os_ = oracle.sketch_batch(b"".join(seqs), offsets_of(seqs), k, w, threads=threads)
     assert np.array_equal(off, ooff), "per-sequence minimizer counts differ"
     assert np.array_equal(p, op), "positions differ"
     assert np.array_equal(h, oh), "hashes differ"
     assert np.array_equal(s, os_), "strands differ"
     return len(h)
+
+
+def check_sketch(dev, seqs, k, w, threads=0, info=None):
+    """Device sketch == oracle sketch (offsets, hashes, positions, strands).  info (dict): strips / redo_strips of the run."""
+    with dev.batch(seqs) as b, dev.sketch(b, k, w) as sk:
+        return verify_sketch(sk, seqs, k, w, threads=threads, info=info)
+
+
+ACGT = np.frombuffer(b"ACGT", np.uint8)
+
+
+def random_bases(rng, n):
+    return bytes(ACGT[rng.integers(0, 4, n)])
+
+
+def of_kmers(rng, m, k):
+    """a random sequence of m k-mers (none for m <= 0: k - 1 + m bases)"""
+    return random_bases(rng, max(m + k - 1, 0))
+
+
+def special_reads(rng):
+    """N runs (multi-run strips: the exact pass's walk over the run table) and low complexity (a minimizer per base; strips the
+    32-bit passes give up wholesale)."""
+    _rnd = random_bases
+    withn = [_rnd(rng, 5000) + b"N" * 7 + _rnd(rng, 12000) + b"NN" + _rnd(rng, 3000), b"N" * 17 + _rnd(rng, 9000) + b"n" * 3 + _rnd(rng, 400)]
+    lowc = [b"A" * 6000 + _rnd(rng, 3000) + b"ACACACAC" * 700 + _rnd(rng, 9000), b"T" * 300, _rnd(rng, 3000) + b"AAC" * 3000 + _rnd(rng, 3000)]
+    return withn, lowc
+
+
+def seam_reads(rng, k, w, nwo, long_strips=20):
+    """Random reads whose lengths sit on the seams of the window pass at (k, w), for strips that own nwo windows: w - 1, w and w + 1
+    k-mers (no, one, two windows); nwo + w - 2, nwo + w - 1 and nwo + w k-mers (one strip exactly full, then the first window of a
+    second strip); 2 nwo + w k-mers; one read of long_strips strips."""
+    ms = [w - 1, w, w + 1, nwo + w - 2, nwo + w - 1, nwo + w, 2 * nwo + w, long_strips * nwo + w - 1 - nwo // 3]
+    return [of_kmers(rng, m, k) for m in ms]
+
+
+def strips_of(seqs, k, w, nwo):
+    """strips the window pass cuts ACGT-only reads into: ceil(windows / nwo) each"""
+    return sum(-(-n // nwo) for n in (len(s) - k + 1 - w + 1 for s in seqs) if n > 0)
 
 
 def small_window_sequences(seed=21, n_long=6, long_len=40000):

@@ -10,16 +10,12 @@ import parity_cases as pc
 K, W = 32, 250
 LONG = 8192                       # ordinals of a long strip
 NWO = (512 - ((W - 16) // 16 + 2)) * 16 - 1   # windows a long strip owns at w = 250: 7935
-ACGT = np.frombuffer(b"ACGT", np.uint8)
-
-
-def _rnd(rng, n):
-    return bytes(ACGT[rng.integers(0, 4, n)])
+_rnd = pc.random_bases
 
 
 def _of_kmers(rng, m, k=K):
     """a random sequence of m k-mers"""
-    return _rnd(rng, m + k - 1)
+    return pc.of_kmers(rng, m, k)
 
 
 def boundary_reads(rng):
@@ -39,12 +35,7 @@ def tail_reads(rng):
     return out
 
 
-def special_reads(rng):
-    """N runs (multi-run strips: the exact pass's walk over the run table) and low complexity (a minimizer per base; strips the
-    32-bit passes give up wholesale)."""
-    withn = [_rnd(rng, 5000) + b"N" * 7 + _rnd(rng, 12000) + b"NN" + _rnd(rng, 3000), b"N" * 17 + _rnd(rng, 9000) + b"n" * 3 + _rnd(rng, 400)]
-    lowc = [b"A" * 6000 + _rnd(rng, 3000) + b"ACACACAC" * 700 + _rnd(rng, 9000), b"T" * 300, _rnd(rng, 3000) + b"AAC" * 3000 + _rnd(rng, 3000)]
-    return withn, lowc
+special_reads = pc.special_reads
 
 
 def both_lengths(dev, monkeypatch, seqs, k=K, w=W):
