@@ -896,6 +896,52 @@ static void batch_on_wstream(ntl_ctx *c, const ntl_batch *b)
     b->packed.touch(SID_W); b->seq_base.touch(SID_W); b->seq_run_first.touch(SID_W); b->run_start.touch(SID_W); b->run_len.touch(SID_W);
 }
 
+/* a batch of nseq sequences and `bases` bases whose packed stream spans `span` positions behind the lead pad */
+static std::unique_ptr<ntl_batch> batch_new(ntl_ctx *c, uint64_t nseq, uint64_t bases, uint64_t span)
+{
+    std::unique_ptr<ntl_batch> b(new ntl_batch());
+    b->c = c; b->nseq = nseq; b->bases = bases;
+    b->total_gpos = NTL_LEAD_PAD + span;
+    b->nwords_packed = (NTL_LEAD_PAD + span + NTL_END_PAD + 15) / 16 + 2;
+    return b;
+}
+
+/* the `--len` column on the device, from b->seq_len (queued on MAIN: b->seq_len outlives the copy) */
+static int batch_upload_seq_len(ntl_ctx *c, ntl_batch *b)
+{
+    int rc;
+    if ((rc = b->seq_len_dev.alloc(c, (b->nseq + 1) * 4))) return rc;
+    if (b->nseq) HIPCHK(c, hipMemcpyAsync(b->seq_len_dev.p, b->seq_len.data(), b->nseq * 4, hipMemcpyHostToDevice, c->stream));
+    b->d_seq_len = b->seq_len_dev.as<uint32_t>();
+    return NTL_OK;
+}
+
+/* the device tables of a batch that arrives packed with its run tables: allocated, uploaded and waited for (the caller's arrays are free again) */
+static int batch_upload_packed(ntl_ctx *c, ntl_batch *b, const uint32_t *packed, const std::vector<uint64_t> &seq_base,
+                               const uint32_t *seq_run_first, const uint32_t *run_start, const uint32_t *run_len)
+{
+    const uint64_t nseq = b->nseq, nruns = b->nruns;
+    int rc;
+    (void)hipSetDevice(c->device);
+    if ((rc = b->packed.alloc(c, b->nwords_packed * 4)) || (rc = b->seq_base.alloc(c, (nseq + 1) * 8)) ||
+        (rc = b->seq_run_first.alloc(c, (nseq + 1) * 4)) || (rc = b->run_start.alloc(c, (nruns + 1) * 4)) ||
+        (rc = b->run_len.alloc(c, (nruns + 1) * 4)))
+        return rc;
+    {
+        ProfSpan span(c, "batch_pack");
+        HIPCHK(c, hipMemcpyAsync(b->packed.p, packed, b->nwords_packed * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b->seq_base.p, seq_base.data(), (nseq + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(b->seq_run_first.p, seq_run_first, (nseq + 1) * 4, hipMemcpyHostToDevice, c->stream));
+        if ((rc = batch_upload_seq_len(c, b))) return rc;
+        if (nruns) {
+            HIPCHK(c, hipMemcpyAsync(b->run_start.p, run_start, nruns * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(b->run_len.p, run_len, nruns * 4, hipMemcpyHostToDevice, c->stream));
+        }
+    }
+    HIPCHK(c, main_wait(c));
+    return NTL_OK;
+}
+
 /* Host arrays in, device layout out: the bases travel as they are (one byte each) and are packed and
  * scanned for ACGT runs on the device (pack_kernels.h).  Pinned memory from ntl_host_alloc makes the
  * copy a single DMA; anything else goes through the runtime's staging buffers. */
@@ -910,13 +956,8 @@ extern "C" int ntl_batch_create(ntl_ctx *c, const char *seqs, const uint64_t *of
     }
     const uint64_t o0 = nseq ? off[0] : 0;
     const uint64_t total = nseq ? off[nseq] - o0 : 0;
-    std::unique_ptr<ntl_batch> b(new ntl_batch());
-    b->c = c;
-    b->nseq = nseq;
-    b->bases = total;
-    b->total_gpos = NTL_LEAD_PAD + total;
-    const uint64_t nwords = (NTL_LEAD_PAD + total + NTL_END_PAD + 15) / 16 + 2;
-    b->nwords_packed = nwords;
+    std::unique_ptr<ntl_batch> b = batch_new(c, nseq, total, total);
+    const uint64_t nwords = b->nwords_packed;
     std::vector<uint64_t> seq_base(nseq + 1);
     b->seq_len.resize(nseq);
     for (uint64_t i = 0; i <= nseq; i++) seq_base[i] = NTL_LEAD_PAD + ((i < nseq ? off[i] : off[nseq]) - o0);
@@ -937,9 +978,7 @@ extern "C" int ntl_batch_create(ntl_ctx *c, const char *seqs, const uint64_t *of
     ProfSpan span(c, "batch_pack");
     if (total) HIPCHK(c, hipMemcpyAsync(raw.p, seqs + o0, total, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(b->seq_base.p, seq_base.data(), (nseq + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = b->seq_len_dev.alloc(c, (nseq + 1) * 4))) return rc;
-    if (nseq) HIPCHK(c, hipMemcpyAsync(b->seq_len_dev.p, b->seq_len.data(), nseq * 4, hipMemcpyHostToDevice, c->stream));
-    b->d_seq_len = b->seq_len_dev.as<uint32_t>();
+    if ((rc = batch_upload_seq_len(c, b.get()))) return rc;
     HIPCHK(c, hipMemsetAsync(b->packed.p, 0, nwords * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(valid32.p, 0, (n32 + 2) * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(ss32.p, 0, (n32 + 2) * 4, c->stream));
@@ -993,9 +1032,7 @@ extern "C" int ntl_batch_create_packed(ntl_ctx *c, const uint32_t *packed, const
     if (nseq >= ((uint64_t)1 << 31)) return fail(c, NTL_EINVAL, "too many sequences in one batch");
     if (nruns >= 0xFFFFFFF0ull) return fail(c, NTL_EINVAL, "too many ACGT runs in one batch");
     if (off[0] != 0) return fail(c, NTL_EINVAL, "offsets[0] must be 0 for a packed batch");
-    std::unique_ptr<ntl_batch> b(new ntl_batch());
-    b->c = c;
-    b->nseq = nseq;
+    std::unique_ptr<ntl_batch> b = batch_new(c, nseq, off[nseq], off[nseq]);
     b->seq_len.resize(nseq);
     std::vector<uint64_t> seq_base(nseq + 1);
     bool multi = false;
@@ -1008,33 +1045,9 @@ extern "C" int ntl_batch_create_packed(ntl_ctx *c, const uint32_t *packed, const
         seq_base[i] = NTL_LEAD_PAD + off[i];
     }
     if (seq_run_first[0] != 0 || seq_run_first[nseq] != nruns) return fail(c, NTL_EINVAL, "seq_run_first does not match the run count");
-    const uint64_t total = off[nseq];
-    seq_base[nseq] = NTL_LEAD_PAD + total;
-    b->bases = total;
-    b->total_gpos = NTL_LEAD_PAD + total;
-    b->nruns = nruns;
-    b->any_multi = multi;
-    b->nwords_packed = (NTL_LEAD_PAD + total + NTL_END_PAD + 15) / 16 + 2;
-    (void)hipSetDevice(c->device);
-    int rc;
-    if ((rc = b->packed.alloc(c, b->nwords_packed * 4)) || (rc = b->seq_base.alloc(c, (nseq + 1) * 8)) ||
-        (rc = b->seq_run_first.alloc(c, (nseq + 1) * 4)) || (rc = b->run_start.alloc(c, (nruns + 1) * 4)) ||
-        (rc = b->run_len.alloc(c, (nruns + 1) * 4)))
-        return rc;
-    {
-        ProfSpan span(c, "batch_pack");
-        HIPCHK(c, hipMemcpyAsync(b->packed.p, packed, b->nwords_packed * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(b->seq_base.p, seq_base.data(), (nseq + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(b->seq_run_first.p, seq_run_first, (nseq + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        if ((rc = b->seq_len_dev.alloc(c, (nseq + 1) * 4))) return rc;
-        if (nseq) HIPCHK(c, hipMemcpyAsync(b->seq_len_dev.p, b->seq_len.data(), nseq * 4, hipMemcpyHostToDevice, c->stream));
-        b->d_seq_len = b->seq_len_dev.as<uint32_t>();
-        if (nruns) {
-            HIPCHK(c, hipMemcpyAsync(b->run_start.p, run_start, nruns * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(b->run_len.p, run_len, nruns * 4, hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    HIPCHK(c, main_wait(c)); /* the caller's arrays and seq_base are free again */
+    seq_base[nseq] = NTL_LEAD_PAD + off[nseq];
+    b->nruns = nruns; b->any_multi = multi;
+    if (int rc = batch_upload_packed(c, b.get(), packed, seq_base, seq_run_first, run_start, run_len)) return rc;
     *out = b.release();
     return NTL_OK;
 }
@@ -1052,10 +1065,6 @@ extern "C" int ntl_batch_create_packed_at(ntl_ctx *c, const uint32_t *packed, ui
     if (nseq >= ((uint64_t)1 << 31)) return fail(c, NTL_EINVAL, "too many sequences in one batch");
     if (nruns >= 0xFFFFFFF0ull) return fail(c, NTL_EINVAL, "too many ACGT runs in one batch");
     if (span_positions >= 0xFFFFFFF0ull - NTL_END_PAD) return fail(c, NTL_EINVAL, "packed stream longer than 2^32 positions");
-    std::unique_ptr<ntl_batch> b(new ntl_batch());
-    b->c = c;
-    b->nseq = nseq;
-    b->seq_len.assign(lengths, lengths + nseq);
     std::vector<uint64_t> seq_base(nseq + 1);
     bool multi = false;
     uint64_t total = 0, prev_end = 0;
@@ -1069,30 +1078,10 @@ extern "C" int ntl_batch_create_packed_at(ntl_ctx *c, const uint32_t *packed, ui
     }
     if (seq_run_first[0] != 0 || seq_run_first[nseq] != nruns) return fail(c, NTL_EINVAL, "seq_run_first does not match the run count");
     seq_base[nseq] = NTL_LEAD_PAD + span_positions;
-    b->bases = total;
-    b->total_gpos = NTL_LEAD_PAD + span_positions;
-    b->nruns = nruns;
-    b->any_multi = multi;
-    b->nwords_packed = (NTL_LEAD_PAD + span_positions + NTL_END_PAD + 15) / 16 + 2;
-    (void)hipSetDevice(c->device);
-    int rc;
-    if ((rc = b->packed.alloc(c, b->nwords_packed * 4)) || (rc = b->seq_base.alloc(c, (nseq + 1) * 8)) ||
-        (rc = b->seq_run_first.alloc(c, (nseq + 1) * 4)) || (rc = b->run_start.alloc(c, (nruns + 1) * 4)) ||
-        (rc = b->run_len.alloc(c, (nruns + 1) * 4)) || (rc = b->seq_len_dev.alloc(c, (nseq + 1) * 4)))
-        return rc;
-    {
-        ProfSpan span(c, "batch_pack");
-        HIPCHK(c, hipMemcpyAsync(b->packed.p, packed, b->nwords_packed * 4, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(b->seq_base.p, seq_base.data(), (nseq + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(b->seq_run_first.p, seq_run_first, (nseq + 1) * 4, hipMemcpyHostToDevice, c->stream));
-        if (nseq) HIPCHK(c, hipMemcpyAsync(b->seq_len_dev.p, b->seq_len.data(), nseq * 4, hipMemcpyHostToDevice, c->stream));
-        b->d_seq_len = b->seq_len_dev.as<uint32_t>();
-        if (nruns) {
-            HIPCHK(c, hipMemcpyAsync(b->run_start.p, run_start, nruns * 4, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(b->run_len.p, run_len, nruns * 4, hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    HIPCHK(c, main_wait(c)); /* the caller's arrays and seq_base are free again */
+    std::unique_ptr<ntl_batch> b = batch_new(c, nseq, total, span_positions);
+    b->seq_len.assign(lengths, lengths + nseq);
+    b->nruns = nruns; b->any_multi = multi;
+    if (int rc = batch_upload_packed(c, b.get(), packed, seq_base, seq_run_first, run_start, run_len)) return rc;
     *out = b.release();
     return NTL_OK;
 }
@@ -1123,11 +1112,7 @@ extern "C" uint64_t ntl_batch_bases(const ntl_batch *b) { return b ? b->bases : 
 static int synth_layout(ntl_ctx *c, const uint32_t *len, uint64_t nseq, std::unique_ptr<ntl_batch> &b, std::vector<uint64_t> &seq_base)
 {
     if (nseq >= ((uint64_t)1 << 31)) return fail(c, NTL_EINVAL, "too many sequences in one batch");
-    b.reset(new ntl_batch());
-    b->c = c;
-    b->nseq = nseq;
     seq_base.resize(nseq + 1);
-    b->seq_len.assign(len, len + nseq);
     uint64_t total = 0;
     for (uint64_t i = 0; i < nseq; i++) {
         if (len[i] == 0 || len[i] >= 0xFFFFFFF0u) return fail(c, NTL_EINVAL, "synthetic sequences must hold 1..2^32-17 bases");
@@ -1135,11 +1120,9 @@ static int synth_layout(ntl_ctx *c, const uint32_t *len, uint64_t nseq, std::uni
         total += len[i];
     }
     seq_base[nseq] = NTL_LEAD_PAD + total;
-    b->bases = total;
-    b->total_gpos = NTL_LEAD_PAD + total;
+    b = batch_new(c, nseq, total, total);
+    b->seq_len.assign(len, len + nseq);
     b->nruns = nseq;
-    b->nwords_packed = (NTL_LEAD_PAD + total + NTL_END_PAD + 15) / 16 + 2;
-    b->any_multi = false;
     int rc;
     if ((rc = b->packed.alloc(c, b->nwords_packed * 4)) || (rc = b->seq_base.alloc(c, (nseq + 1) * 8)) ||
         (rc = b->seq_run_first.alloc(c, (nseq + 1) * 4)) || (rc = b->run_start.alloc(c, (nseq + 1) * 4)) ||
@@ -1669,7 +1652,7 @@ static int window_plan(ntl_ctx *c, const ntl_batch *b, int k, int w, bool no_lis
         P.shape = WS_8_19_7_L128;
         if (P.lists) P.beside = 24u;
     } else if (P.expected_per_strip <= WP_FIT_11_4) { /* w >= 235 at ten candidates per window */
-        /* (lists, round 5: the other stream's emit_list_kernel keeps to two resident workgroups per CU -- sketch_enqueue --
+        /* (lists, round 5: the other stream's emit_list_kernel keeps to two resident workgroups per CU -- emit_grid --
            and the window stage takes 24 of the 32 wavefront slots: C3 70.7 ms per step against 75.9 at 16 and 82.5 at
            32, profiles/r05_share_sweep_C3.jsonl) */
         P.shape = wave == 4 ? WS_4_11_4 : (wave == 16 ? WS_16_11_4 : WS_8_11_4);
@@ -1718,7 +1701,7 @@ static void launch_window_pass(ntl_ctx *c, const WindowPlan &P, const Sketch2Arg
             wgs = (wgs + 7u) & ~7u;
             /* Two streams, NTL_SKW_BUDGET chunks per wavefront: short-lived workgroups, as many as it takes, that fill what
                the other stream's kernels leave free (those have the higher stream priority and a bounded number of
-               resident workgroups: sketch_enqueue, emit) -- and the whole CU while that stream has nothing to run. */
+               resident workgroups: emit_grid) -- and the whole CU while that stream has nothing to run. */
             Sketch2Args Bq = B;
             if (P.chunk_budget) {
                 const unsigned per_xcd_chunks = (((strips + 7u) >> 3) + SKW_CHUNK - 1u) / SKW_CHUNK;
@@ -1743,293 +1726,308 @@ static void launch_window_pass(ntl_ctx *c, const WindowPlan &P, const Sketch2Arg
     });
 }
 
+/* What one sketch_enqueue holds between its stages.  The temporaries return to the context's cache when it ends: every later user of
+ * those blocks is queued behind the kernels of this sketch on the stream they were used on, so no wait is needed. */
+struct SketchWork {
+    int wsid; hipStream_t ws, ms; /* the window stage's stream id (MAIN when the pipeline is off), its stream, MAIN */
+    uint64_t nmask; /* words of the bitmask: one bit per base */
+    DevBuf run_n, run_ord, seq_M, nstrips, strip_first, tile, redo, strip_tab; /* (nstrips / strip_first: nseq+1 entries, the scan leaves the total behind the last) */
+    SeqTables T; StripLists Ls = {}; StripZero Z = {};
+    DevBuf lcnt, lent, loff;
+    struct Mask : CleanMask { /* error paths: the mask is not known to be clean any more, it is freed and not kept */
+        ntl_ctx *c = nullptr;
+        ~Mask() { if (p) dev_free(c, p, bytes); }
+    } mask;
+    DevBuf strip_lite;
+};
+static const uint64_t REDO_HEAD = 16 + 8 * 16; /* words in front of the two lists of `redo` */
+
+/* Preparation, on the window stream in front of the window kernels: the temporaries, the batch's tables, the strips' tables */
+static int sketch_prepare(ntl_ctx *c, const ntl_batch *b, int k, int w, const WindowPlan &P, ntl_sketch *s, SketchWork &W)
+{
+    const uint64_t nseq = b->nseq, ub_strips = P.strips;
+    const int wsid = W.wsid;
+    int rc;
+    W.nmask = (b->total_gpos + 31) / 32 + 1;
+    if ((rc = W.run_n.alloc(c, (b->nruns + 1) * 4, wsid)) || (rc = W.run_ord.alloc(c, (b->nruns + 1) * 4, wsid)) ||
+        (rc = W.seq_M.alloc(c, (nseq + 1) * 4, wsid)) || (rc = W.nstrips.alloc(c, (nseq + 1) * 4, wsid)) ||
+        (rc = W.strip_first.alloc(c, (nseq + 2) * 4, wsid)) || (rc = s->mx_off.alloc(c, (nseq + 1) * 4)) ||
+        (rc = s->sums.alloc(c, sizeof(SketchSums), wsid))) return rc;
+    s->sums.touch(SID_MAIN); /* zeroed by strip_table_kernel on the window stream, added to and read on MAIN */
+    batch_on_wstream(c, b);
+    SeqTables &T = W.T;
+    T.packed = b->packed.as<uint32_t>(); T.seq_base = b->seq_base.as<uint64_t>();
+    T.seq_run_first = b->seq_run_first.as<uint32_t>(); T.run_start = b->run_start.as<uint32_t>();
+    T.run_len = b->run_len.as<uint32_t>(); T.nseq = (uint32_t)nseq;
+    StripLists &Ls = W.Ls;
+    if (P.lists) {
+        Ls.slot = P.slot; Ls.ovf_base = (uint32_t)((ub_strips + 1) * P.slot); Ls.ovf_cap = P.pool;
+        /* cnt[ub_strips + 1] (+ the two control words behind it), zeroed: a strip nobody lists has none */
+        if ((rc = W.lcnt.alloc(c, (ub_strips + 4) * 4, wsid)) || (rc = W.lent.alloc(c, ((ub_strips + 1) * P.slot + P.pool) * 4, wsid)) || (rc = W.loff.alloc(c, (ub_strips + 2) * 4))) return rc;
+        W.lcnt.touch(SID_MAIN); W.lent.touch(SID_MAIN);
+        Ls.cnt = W.lcnt.as<uint32_t>(); Ls.ent = W.lent.as<uint32_t>(); Ls.ctl = Ls.cnt + ub_strips + 2;
+    }
+    /* the fast pass's counters and lists: [0] strips for the exact pass, [1] strips the threshold pass gave up, then the eight chunk
+       counters of sketch_wave_kernel (one per XCD's share of the strips, 64 bytes apart), then the two lists.  Zeroed -- with the
+       strips' counts -- by strip_table_kernel: one launch instead of three fills on the window stream's critical path (round 5) */
+    StripZero &Z = W.Z;
+    if (P.fast() && ub_strips) {
+        if ((rc = W.redo.alloc(c, (REDO_HEAD + 2 * ub_strips + 4) * 4, wsid))) return rc;
+        Z.head = W.redo.as<uint32_t>(); Z.nhead = (uint32_t)REDO_HEAD;
+        Z.cnt = Ls.cnt; Z.ncnt = Ls.cnt ? (uint32_t)(ub_strips + 4) : 0u;
+    }
+    W.mask.c = c;
+    if (!P.lists && (rc = mask_take(c, W.nmask * 4, wsid, &W.mask))) return rc;
+    if ((rc = W.strip_tab.alloc(c, (ub_strips + 1) * sizeof(StripInfo), wsid)) || (rc = W.strip_lite.alloc(c, (ub_strips + 1) * sizeof(StripLite), wsid))) return rc;
+    SketchSums *dsums = s->sums.as<SketchSums>();
+    /* the device sums are zeroed by strip_table_kernel (StripZero), in front of the window kernels on their stream; every kernel that
+       writes them runs on MAIN behind the window stage (sketch_enqueue's event; one stream when the pipeline is off).  No sequence, no kernel: a fill */
+    Z.sums = (uint32_t *)dsums; Z.nsums = (uint32_t)(sizeof(SketchSums) / 4);
+    if (!nseq) HIPCHK(c, hipMemsetAsync(dsums, 0, sizeof(SketchSums), W.ms));
+    ProfSpan sp(c, "sketch_meta", wsid);
+    if (nseq) {
+        KTables K;
+        K.run_n = W.run_n.as<uint32_t>(); K.run_ord = W.run_ord.as<uint32_t>();
+        K.seq_M = W.seq_M.as<uint32_t>(); K.seq_nstrips = W.nstrips.as<uint32_t>();
+        hipLaunchKernelGGL(seq_meta_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, W.ws, T, K, k, w, P.G.NWO);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = device_scan(c, W.nstrips.as<uint32_t>(), W.strip_first.as<uint32_t>(), nseq, nullptr, 1, nullptr, wsid))) return rc;
+        hipLaunchKernelGGL(strip_table_kernel, dim3((unsigned)((ub_strips + 255) / 256 + 1)), dim3(256), 0, W.ws, T, (const uint32_t *)K.run_n,
+                           (const uint32_t *)K.run_ord, (const uint32_t *)K.seq_M, (const uint32_t *)W.strip_first.as<uint32_t>(), P.G.NWO,
+                           P.C * P.nt, W.strip_tab.as<StripInfo>(), (uint32_t)ub_strips + 1u, W.strip_lite.as<StripLite>(), Z);
+        HIPCHK(c, hipGetLastError());
+    }
+    return NTL_OK;
+}
+
+/* the k-dependent ring forms of g8 and g4 that the fast window pass reads: built once per k and context, on the window stream in front of their first user */
+static int g8k_for(ntl_ctx *c, int k, hipStream_t ws, uint32_t rev_a, uint32_t rev_b, const uint2 **out)
+{
+    auto it = c->g8k.find(k);
+    if (it == c->g8k.end()) {
+        if (c->g8k.size() >= 8) { /* a caller that sweeps k: start over */
+            HIPCHK(c, sync_both(c));
+            for (auto &kv : c->g8k) (void)hipFree(kv.second);
+            c->g8k.clear();
+        }
+        void *t = nullptr;
+        if (hipMalloc(&t, (size_t)(2 * 65536 + 1024) * sizeof(uint2)) != hipSuccess) return fail(c, NTL_ENOMEM, "hipMalloc failed");
+        hipLaunchKernelGGL(g8k_build_kernel, dim3(256), dim3(256), 0, ws, (const uint64_t (*)[2])c->g8, (uint2 *)t, rev_a, rev_b);
+        hipLaunchKernelGGL(g4k_build_kernel, dim3(1), dim3(256), 0, ws, (const uint64_t (*)[2])c->g4, (uint2 *)t + 2 * 65536, rev_a, rev_b); /* the four-base form, behind it */
+        HIPCHK(c, hipGetLastError());
+        it = c->g8k.emplace(k, t).first;
+    }
+    *out = (const uint2 *)it->second;
+    return NTL_OK;
+}
+
+/* The window stage: the plan's 32-bit pass, the exact pass over what it flagged (redo) and over the multi-run strips; or the exact pass alone */
+static int sketch_window_stage(ntl_ctx *c, const ntl_batch *b, int k, const WindowPlan &P, ntl_sketch *s, SketchWork &W)
+{
+    const uint64_t ub_strips = P.strips;
+    if (!ub_strips) return NTL_OK;
+    const int wsid = W.wsid, nt = P.nt;
+    SketchArgs A = {}; /* (redo_list, redo_count, redo_out: null) */
+    A.T = W.T;
+    A.run_n = W.run_n.as<uint32_t>(); A.run_ord = W.run_ord.as<uint32_t>(); A.seq_M = W.seq_M.as<uint32_t>();
+    A.strip_lite = W.strip_lite.as<StripLite>(); A.strip_tab = W.strip_tab.as<StripInfo>(); A.nstrips = (uint32_t)ub_strips; A.mask = (uint32_t *)W.mask.p; A.G = P.G;
+    make_tables(k, A.roll_tab, A.seed_tab);
+    A.g4 = (const uint64_t (*)[2])c->g4; A.g8 = (const uint64_t (*)[2])c->g8;
+    A.Ls = W.Ls;
+    if (!P.fast()) {
+        ProfSpan sp(c, "sketch_mask", wsid);
+        if (P.pass == WP_SMALL) launch_small(c, A, (unsigned)ub_strips, b->any_multi);
+        else if (P.C == 16) launch_mask<16>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
+        else if (P.C == 4) launch_mask<4>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
+        else launch_mask<1>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
+        HIPCHK(c, hipGetLastError());
+        return NTL_OK;
+    }
+    uint32_t *const redo = W.redo.as<uint32_t>();
+    Sketch2Args B = {};
+    B.A = A;
+    B.thresh = P.thresh; B.dbg = P.dbg; B.force_redo = P.force_redo;
+    B.redo_count = redo; B.fb_count = redo + 1; B.chunk_next = redo + 16;
+    B.redo_list = redo + REDO_HEAD; B.fb_list = B.redo_list + ub_strips + 2;
+    B.max_word = b->nwords_packed - 1;
+    B.q16 = k / 16; B.r16 = k % 16; B.rev_a = (uint32_t)(k - 1) % 33u; B.rev_b = (uint32_t)(k - 1) % 31u;
+    if (int rc = g8k_for(c, k, W.ws, B.rev_a, B.rev_b, &B.g8k)) return rc;
+    B.g4k = B.g8k + 2 * 65536;
+    {
+        ProfSpan sp(c, "sketch_mask", wsid);
+        launch_window_pass(c, P, B);
+        HIPCHK(c, hipGetLastError());
+    }
+    ProfSpan sp(c, "sketch_redo", wsid);
+    SketchArgs R = A;
+    R.redo_count = B.redo_count; R.redo_list = B.redo_list;
+    /* the redo pass writes the two counts into the slot (`redo` never leaves the window stream); s->done, on MAIN behind the
+       emit kernel, is behind it too (window stage -> emit) */
+    R.redo_out = &((SketchSums *)slot_dev(c, s->slot))->redo_n;
+    launch_mask<16>(c, R, (unsigned)ub_strips, true, false, nt);
+    if (b->any_multi) launch_mask<16>(c, A, (unsigned)ub_strips, false, true, nt);
+    HIPCHK(c, hipGetLastError());
+    return NTL_OK;
+}
+
+/* Beside the window stage (two streams) the emit kernel may keep to a bounded number of resident workgroups that take their tiles from
+   counters; alone: one workgroup per tile, as many resident as fit. */
+struct EmitGrid { unsigned grid; bool from_counters; /* the workgroups take their tiles from tile_next */ };
+static EmitGrid emit_grid(bool pipelined, int probe, bool lists, bool dense_windows, int n_cu, uint64_t tiles)
+{
+    /* the direct-slot form (most lookups hit: one random 64-byte line from HBM per minimizer) is bound by the rate of those
+       transactions and gains nothing beyond 12 wavefronts per CU, while the slots it holds are missed by the map kernels
+       and the window stage: C5 296-300 -> 269-271 ms per step at 3 workgroups per CU, 275 at 5, 280 at 4 with other window
+       grids (profiles/r04_share_sweep_C5.jsonl); the tag form (C3) is as fast uncapped (74.4-75.0 against 74.9-75.9) */
+    /* emit_list_kernel (44 registers, 13 KB of LDS) would fill all 32 wavefront slots of a CU, and the window stage's resident
+       workgroups of the next sub-batch then wait for them to drain (C3: 91 ms per step uncapped, 75.9 at two per CU) */
+    /* beside the DENSE window shapes (w < 137: twelve window wavefronts per CU, window_plan) the tag form takes four: C2
+       0.890 -> 0.800 ms per step (0.806 at three, 0.815 uncapped; profiles/r07b_C2_share_sweep.txt) */
+    int per_cu = !pipelined ? 0 : (probe == 2 ? 3 : (lists ? (dense_windows ? 4 : 2) : 0));
+    if (const char *e = getenv("NTL_EMIT_WGS_PER_CU")) per_cu = atoi(e); /* read per call: the tests switch it inside one process */
+    const uint64_t cap = (uint64_t)per_cu * (uint64_t)n_cu;
+    if (per_cu > 0 && cap >= 8 && cap < tiles) return {(unsigned)cap, true};
+    if (per_cu < 0) return {(unsigned)(-per_cu < 8 ? 8 : -per_cu), true}; /* tests: that many workgroups whatever the size */
+    return {(unsigned)tiles, false};
+}
+
+/* the emit kernel of (lists, probe, NTL_EMIT_U, small windows): U -- minimizers in flight per thread -- comes down to a value the form has */
+static void emit_launch(hipStream_t ms, unsigned grid, bool lists, int probe, bool small, const EmitArgs &E, const EmitListArgs &Q)
+{
+    const char *eu = getenv("NTL_EMIT_U"); /* read per call: the tests switch it inside one process */
+    const int emit_u = eu ? atoi(eu) : 1;
+    const dim3 g(grid);
+    if (lists && probe == 0) hipLaunchKernelGGL((emit_list_kernel<0, 1>), g, dim3(EL_NT), 0, ms, E, Q);
+    else if (lists) with_constant<1, 3>(probe, [&](auto p) {
+        constexpr int PROBE = decltype(p)::value;
+        if (emit_u >= 4) hipLaunchKernelGGL((emit_list_kernel<PROBE, 4>), g, dim3(EL_NT), 0, ms, E, Q);
+        else if (emit_u >= 2) hipLaunchKernelGGL((emit_list_kernel<PROBE, 2>), g, dim3(EL_NT), 0, ms, E, Q);
+        else hipLaunchKernelGGL((emit_list_kernel<PROBE, 1>), g, dim3(EL_NT), 0, ms, E, Q);
+    });
+    else if (probe == 0 && (eu ? emit_u >= 4 : small)) hipLaunchKernelGGL((emit_kernel<0, 4, NTL_EMIT_DENSE_CAP>), g, dim3(EMIT_NT), 0, ms, E); /* dense sketches: rounds of 8192, four k-mers' loads in flight per thread */
+    else if (probe == 0 && emit_u >= 2) hipLaunchKernelGGL((emit_kernel<0, 2>), g, dim3(EMIT_NT), 0, ms, E);
+    else if (probe == 0) hipLaunchKernelGGL((emit_kernel<0, 1>), g, dim3(EMIT_NT), 0, ms, E);
+    else with_constant<1, 3>(probe, [&](auto p) {
+        constexpr int PROBE = decltype(p)::value;
+        if (emit_u >= 2) hipLaunchKernelGGL((emit_kernel<PROBE, 2>), g, dim3(EMIT_NT), 0, ms, E);
+        else hipLaunchKernelGGL((emit_kernel<PROBE, 1>), g, dim3(EMIT_NT), 0, ms, E);
+    });
+}
+
+/* The emit stage, on MAIN: the minimizers' ranks (a scan over the strips' list counts or the bitmask's tiles), the records (and the index lookup), the totals */
+static int sketch_emit_stage(ntl_ctx *c, const ntl_batch *b, int k, const WindowPlan &P, const ntl_index *ix, ntl_sketch *s, uint64_t cap, SketchWork &W)
+{
+    const bool lists = P.lists;
+    const uint64_t nseq = b->nseq, ub_strips = P.strips, nmask = W.nmask;
+    hipStream_t ms = W.ms;
+    const StripLists &Ls = W.Ls;
+    SketchSums *dsums = s->sums.as<SketchSums>();
+    int rc;
+    ProfSpan sp(c, "sketch_emit");
+    const uint64_t tiles = lists ? (ub_strips + EL_STRIPS - 1) / EL_STRIPS : (nmask + EMIT_TILE - 1) / EMIT_TILE;
+    DevBuf tile_seq, tile_next;
+    if ((rc = tile_next.alloc(c, 8 * 16 * 4))) return rc;
+    if (lists) {
+        /* ranks: a scan over one count per strip; the total (or, if the lists ran out of pool, a total no array holds: the map
+           kernels leave such a sketch alone and sketch_finalize makes it again through the bitmask) */
+        W.strip_first.touch(SID_MAIN); W.strip_tab.touch(SID_MAIN);
+        if ((rc = device_scan(c, Ls.cnt, W.loff.as<uint32_t>(), ub_strips, nullptr, 1, &dsums->total_mx))) return rc;
+        SketchSums *hd = (SketchSums *)slot_dev(c, s->slot); /* the true total and whether the lists ran out, for the host */
+        hipLaunchKernelGGL(list_fail_kernel, dim3(1), dim3(64), 0, ms, (const uint32_t *)Ls.ctl, &dsums->total_mx, &dsums->list_fail, tile_next.as<uint32_t>(),
+                           &hd->total_mx, &hd->list_fail);
+        hipLaunchKernelGGL(mx_off_from_strips_kernel, dim3((unsigned)((nseq + 256) / 256)), dim3(256), 0, ms, (const uint32_t *)W.strip_first.as<uint32_t>(),
+                           (const uint32_t *)W.loff.as<uint32_t>(), (uint32_t)nseq, s->mx_off.as<uint32_t>());
+    } else {
+        if ((rc = W.tile.alloc(c, tiles * 4)) || (rc = tile_seq.alloc(c, (tiles + 2) * 4))) return rc;
+        if (nseq)
+            hipLaunchKernelGGL(tile_seq_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, ms, (const uint64_t *)W.T.seq_base, (uint32_t)nseq, tiles, tile_seq.as<uint32_t>());
+        hipLaunchKernelGGL(mask_count_kernel, dim3((unsigned)tiles), dim3(EMIT_NT), 0, ms, (const uint32_t *)W.mask.p, nmask, W.tile.as<uint32_t>(), tile_next.as<uint32_t>());
+        hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(SCAN_NT), 0, ms, W.tile.as<uint32_t>(), tiles, &dsums->total_mx, (uint64_t)0, (uint32_t *)nullptr);
+    }
+    HIPCHK(c, hipGetLastError());
+    if (!s->no_records && (rc = s->records.alloc(c, cap * sizeof(MxRecord)))) return rc;
+    s->cap = cap;
+    const int probe = !ix ? 0 : (ix->hit_fraction->load(std::memory_order_relaxed) <= 0.5f ? 1 : 2); /* tags first unless the last batch on this index mostly hit */
+    if (ix) {
+        if ((rc = s->rpos.alloc(c, cap * 4)) || (rc = s->cand.alloc(c, cap * sizeof(Cand)))) return rc;
+        s->cand_gen = ix->gen;
+        if (ix->c != c && ix->built) HIPCHK(c, hipStreamWaitEvent(ms, ix->built, 0));
+    }
+    EmitArgs E = {};
+    E.packed = W.T.packed; E.seq_base = W.T.seq_base; E.nseq = (uint32_t)nseq; E.mask = (uint32_t *)W.mask.p;
+    E.nwords = nmask; E.tile_off = W.tile.as<uint32_t>(); E.tile_seq = tile_seq.as<uint32_t>(); E.mx_off = s->mx_off.as<uint32_t>();
+    E.out = s->no_records ? nullptr : s->records.as<MxRecord>(); E.out_cap = (uint32_t)cap;
+    E.k = k; E.mult = 1ull ^ ((uint64_t)k * 0x90b45d39fb6da1faull);
+    uint64_t roll[16][2];
+    make_tables(k, roll, E.seed_tab);
+    E.g4 = (const uint64_t (*)[2])c->g4; E.g8 = (const uint64_t (*)[2])c->g8;
+    if (ix) { /* (else no lookup: those pointers stay null) */
+        E.rpos = s->rpos.as<uint32_t>();
+        E.slots = ix->slots.as<IndexSlot>(); E.tags = ix->tags.as<uint8_t>(); E.special = ix->special.as<IndexSpecial>();
+        E.ix_bits = ix->bits; E.cand = s->cand.as<Cand>(); E.nfound = &dsums->nfound;
+    }
+    const EmitGrid eg = emit_grid(c->pipelined, probe, lists, P.dense_windows, c->n_cu, tiles);
+    E.ntiles = (uint32_t)tiles; E.tile_next = eg.from_counters ? tile_next.as<uint32_t>() : nullptr;
+    EmitListArgs Q = {};
+    if (lists) { Q.Ls = Ls; Q.strip_tab = W.strip_tab.as<StripInfo>(); Q.strip_off = W.loff.as<uint32_t>(); Q.nstrips = (uint32_t)ub_strips; }
+    emit_launch(ms, eg.grid, lists, probe, P.pass == WP_SMALL, E, Q);
+    HIPCHK(c, hipGetLastError());
+    /* the emit kernel is the last reader of the bitmask and clears the words it read: the mask goes back clean */
+    if (W.mask.p) {
+        CleanMask m = W.mask;
+        m.clean = sev_get(c);
+        if (m.clean) HIPCHK(c, hipEventRecord(m.clean, ms));
+        else HIPCHK(c, hipStreamSynchronize(ms));
+        c->masks.push_back(m);
+        W.mask.p = nullptr; /* handed over */
+    }
+    /* (the map kernels read the lengths of the sketched sequences from the batch itself: ntl_map_run holds it) */
+    s->nfound_owed = false;
+    if (!lists) { /* the bitmask path (off the hot path): the totals come back by copies */
+        SketchSums *hs = (SketchSums *)s->slot;
+        HIPCHK(c, hipMemcpyAsync(&hs->total_mx, &dsums->total_mx, 4, hipMemcpyDeviceToHost, ms));
+        if (ix) HIPCHK(c, hipMemcpyAsync(&hs->nfound, &dsums->nfound, 8, hipMemcpyDeviceToHost, ms));
+    } else s->nfound_owed = ix != nullptr; /* (list_fail_kernel wrote the total and the flag) */
+    return NTL_OK;
+}
+
 /* Queues one sketch: the window stage on the window stream, count + emit (+ index lookup) on MAIN behind it.  Nothing
  * waits; the minimizer total lands in the sketch's page-locked slot and s->done is recorded behind it.  `cap` = records the
  * arrays hold: a guess from the expected density (sketch_finalize makes the sketch again if the batch was denser), or the
  * exact total on that second round. */
 static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const ntl_index *ix, ntl_sketch *s, uint64_t cap)
 {
+    /* the host runs at most 8 sketches ahead of the device */
+    hipEvent_t &throttle = c->throttle[c->n_enqueued & 7u];
+    if (throttle) (void)hipEventSynchronize(throttle);
+    reap(c, false);
     WindowPlan P;
     int rc;
     if ((rc = window_plan(c, b, k, w, s->no_lists, P))) return rc;
-    const SketchGeom &G = P.G;
-    const int C = P.C, nt = P.nt;
-    const bool fast = P.fast(), lists = P.lists;
-    const uint64_t nseq = b->nseq, ub_strips = P.strips;
-    const int wsid = c->sid(SID_W);
-    hipStream_t ws = c->s(wsid), ms = c->stream;
-    /* the host runs at most 8 sketches ahead of the device */
-    {
-        hipEvent_t &t = c->throttle[c->n_enqueued & 7u];
-        if (t) (void)hipEventSynchronize(t);
-        reap(c, false);
-    }
-    DevBuf run_n, run_ord, seq_M, nstrips, strip_first, tile, redo, strip_tab;
-    /* nstrips / strip_first hold nseq+1 entries: the scan leaves the total behind the last one */
-    const uint64_t nmask = (b->total_gpos + 31) / 32 + 1;
-    /* the preparation's arrays: made on the window stream, where its kernels run in front of the window kernels */
-    if ((rc = run_n.alloc(c, (b->nruns + 1) * 4, wsid)) || (rc = run_ord.alloc(c, (b->nruns + 1) * 4, wsid)) ||
-        (rc = seq_M.alloc(c, (nseq + 1) * 4, wsid)) || (rc = nstrips.alloc(c, (nseq + 1) * 4, wsid)) ||
-        (rc = strip_first.alloc(c, (nseq + 2) * 4, wsid)) || (rc = s->mx_off.alloc(c, (nseq + 1) * 4)) ||
-        (rc = s->sums.alloc(c, sizeof(SketchSums), wsid))) {
-        return rc;
-    }
-    s->sums.touch(SID_MAIN); /* zeroed by strip_table_kernel on the window stream, added to and read on MAIN */
-    batch_on_wstream(c, b);
-    SeqTables T;
-    T.packed = b->packed.as<uint32_t>(); T.seq_base = b->seq_base.as<uint64_t>();
-    T.seq_run_first = b->seq_run_first.as<uint32_t>(); T.run_start = b->run_start.as<uint32_t>();
-    T.run_len = b->run_len.as<uint32_t>(); T.nseq = (uint32_t)nseq;
-    StripLists Ls;
-    memset(&Ls, 0, sizeof Ls);
-    DevBuf lcnt, lent, loff;
-    if (lists) {
-        Ls.slot = P.slot; Ls.ovf_base = (uint32_t)((ub_strips + 1) * P.slot); Ls.ovf_cap = P.pool;
-        /* cnt[ub_strips + 1] (+ the two control words behind it), zeroed: a strip nobody lists has none */
-        if ((rc = lcnt.alloc(c, (ub_strips + 4) * 4, wsid)) || (rc = lent.alloc(c, ((ub_strips + 1) * P.slot + P.pool) * 4, wsid)) ||
-            (rc = loff.alloc(c, (ub_strips + 2) * 4))) return rc;
-        lcnt.touch(SID_MAIN); lent.touch(SID_MAIN);
-        Ls.cnt = lcnt.as<uint32_t>(); Ls.ent = lent.as<uint32_t>(); Ls.ctl = Ls.cnt + ub_strips + 2;
-    }
-    /* the fast pass's counters and lists: [0] strips for the exact pass, [1] strips the threshold pass gave up, then the eight chunk
-       counters of sketch_wave_kernel (one per XCD's share of the strips, 64 bytes apart), then the two lists.  Zeroed -- with the
-       strips' counts -- by strip_table_kernel: one launch instead of three fills on the window stream's critical path (round 5) */
-    StripZero Z;
-    memset(&Z, 0, sizeof Z);
-    const uint64_t redo_head = 16 + 8 * 16; /* words in front of the lists */
-    if (fast && ub_strips) {
-        if ((rc = redo.alloc(c, (redo_head + 2 * ub_strips + 4) * 4, wsid))) return rc;
-        Z.head = redo.as<uint32_t>(); Z.nhead = (uint32_t)redo_head;
-        Z.cnt = Ls.cnt; Z.ncnt = Ls.cnt ? (uint32_t)(ub_strips + 4) : 0u;
-    }
-    CleanMask mask;
-    if (!lists && (rc = mask_take(c, nmask * 4, wsid, &mask))) return rc;
-    struct MaskGuard { /* error paths: the mask is not known to be clean any more */
-        ntl_ctx *c; CleanMask *m;
-        ~MaskGuard() { if (m->p) { dev_free(c, m->p, m->bytes); m->p = nullptr; } }
-    } mask_guard{c, &mask};
-    if ((rc = strip_tab.alloc(c, (ub_strips + 1) * sizeof(StripInfo), wsid))) return rc;
-    DevBuf strip_lite;
-    if ((rc = strip_lite.alloc(c, (ub_strips + 1) * sizeof(StripLite), wsid))) return rc;
-    SketchSums *dsums = s->sums.as<SketchSums>();
-    /* the device sums are zeroed by strip_table_kernel (StripZero), in front of the window kernels on their stream; every kernel that
-       writes them runs on MAIN behind the window stage (the event below; one stream when the pipeline is off).  No sequence, no kernel: a fill */
-    Z.sums = (uint32_t *)dsums; Z.nsums = (uint32_t)(sizeof(SketchSums) / 4);
-    if (!nseq) HIPCHK(c, hipMemsetAsync(dsums, 0, sizeof(SketchSums), ms));
-    {
-        ProfSpan sp(c, "sketch_meta", wsid);
-        if (nseq) {
-            KTables K;
-            K.run_n = run_n.as<uint32_t>(); K.run_ord = run_ord.as<uint32_t>();
-            K.seq_M = seq_M.as<uint32_t>(); K.seq_nstrips = nstrips.as<uint32_t>();
-            hipLaunchKernelGGL(seq_meta_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, ws, T, K, k, w, G.NWO);
-            HIPCHK(c, hipGetLastError());
-            if ((rc = device_scan(c, nstrips.as<uint32_t>(), strip_first.as<uint32_t>(), nseq, nullptr, 1, nullptr, wsid))) return rc;
-            hipLaunchKernelGGL(strip_table_kernel, dim3((unsigned)((ub_strips + 255) / 256 + 1)), dim3(256), 0, ws, T,
-                               (const uint32_t *)run_n.as<uint32_t>(), (const uint32_t *)run_ord.as<uint32_t>(),
-                               (const uint32_t *)seq_M.as<uint32_t>(), (const uint32_t *)strip_first.as<uint32_t>(), G.NWO,
-                               C * nt, strip_tab.as<StripInfo>(), (uint32_t)ub_strips + 1u, strip_lite.as<StripLite>(), Z);
-            HIPCHK(c, hipGetLastError());
-        }
-    }
-    if (ub_strips) {
-        SketchArgs A;
-        A.T = T;
-        A.run_n = run_n.as<uint32_t>(); A.run_ord = run_ord.as<uint32_t>(); A.seq_M = seq_M.as<uint32_t>();
-        A.strip_lite = strip_lite.as<StripLite>();
-        A.strip_tab = strip_tab.as<StripInfo>(); A.nstrips = (uint32_t)ub_strips; A.mask = (uint32_t *)mask.p; A.G = G;
-        make_tables(k, A.roll_tab, A.seed_tab);
-        A.g4 = (const uint64_t (*)[2])c->g4;
-        A.g8 = (const uint64_t (*)[2])c->g8;
-        A.redo_list = nullptr; A.redo_count = nullptr; A.redo_out = nullptr;
-        A.Ls = Ls;
-        if (fast) {
-            Sketch2Args B;
-            memset(&B, 0, sizeof B);
-            B.A = A;
-            B.thresh = P.thresh; B.dbg = P.dbg; B.force_redo = P.force_redo;
-            B.redo_count = redo.as<uint32_t>(); B.fb_count = redo.as<uint32_t>() + 1;
-            B.chunk_next = redo.as<uint32_t>() + 16;
-            B.redo_list = redo.as<uint32_t>() + redo_head; B.fb_list = B.redo_list + ub_strips + 2;
-            B.chunk_budget = 0;
-            B.max_word = b->nwords_packed - 1;
-            B.q16 = k / 16; B.r16 = k % 16;
-            B.rev_a = (uint32_t)(k - 1) % 33u; B.rev_b = (uint32_t)(k - 1) % 31u;
-            {
-                auto it = c->g8k.find(k);
-                if (it == c->g8k.end()) { /* built once per k and context, on the window stream in front of its first user */
-                    if (c->g8k.size() >= 8) { /* a caller that sweeps k: start over */
-                        HIPCHK(c, sync_both(c));
-                        for (auto &kv : c->g8k) (void)hipFree(kv.second);
-                        c->g8k.clear();
-                    }
-                    void *t = nullptr;
-                    if (hipMalloc(&t, (size_t)(2 * 65536 + 1024) * sizeof(uint2)) != hipSuccess) return fail(c, NTL_ENOMEM, "hipMalloc failed");
-                    hipLaunchKernelGGL(g8k_build_kernel, dim3(256), dim3(256), 0, ws, (const uint64_t (*)[2])c->g8, (uint2 *)t,
-                                       B.rev_a, B.rev_b);
-                    hipLaunchKernelGGL(g4k_build_kernel, dim3(1), dim3(256), 0, ws, (const uint64_t (*)[2])c->g4, (uint2 *)t + 2 * 65536,
-                                       B.rev_a, B.rev_b); /* the four-base form of the same, behind it */
-                    HIPCHK(c, hipGetLastError());
-                    it = c->g8k.emplace(k, t).first;
-                }
-                B.g8k = (const uint2 *)it->second;
-                B.g4k = B.g8k + 2 * 65536;
-            }
-            {
-                ProfSpan sp(c, "sketch_mask", wsid);
-                launch_window_pass(c, P, B);
-                HIPCHK(c, hipGetLastError());
-            }
-            ProfSpan sp(c, "sketch_redo", wsid);
-            SketchArgs R = A;
-            R.redo_count = B.redo_count; R.redo_list = B.redo_list;
-            /* the redo pass writes the two counts into the slot (`redo` never leaves the window stream); s->done, on MAIN behind the
-               emit kernel, is behind it too (window stage -> emit) */
-            R.redo_out = &((SketchSums *)slot_dev(c, s->slot))->redo_n;
-            launch_mask<16>(c, R, (unsigned)ub_strips, true, false, nt);
-            if (b->any_multi) launch_mask<16>(c, A, (unsigned)ub_strips, false, true, nt);
-            HIPCHK(c, hipGetLastError());
-        } else {
-            ProfSpan sp(c, "sketch_mask", wsid);
-            if (P.pass == WP_SMALL) launch_small(c, A, (unsigned)ub_strips, b->any_multi);
-            else if (C == 16) launch_mask<16>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
-            else if (C == 4) launch_mask<4>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
-            else launch_mask<1>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
-            HIPCHK(c, hipGetLastError());
-        }
-    }
-    if (ws != ms) { /* window stage -> emit */
+    SketchWork W;
+    W.wsid = c->sid(SID_W); W.ws = c->s(W.wsid); W.ms = c->stream;
+    if ((rc = sketch_prepare(c, b, k, w, P, s, W))) return rc;
+    if ((rc = sketch_window_stage(c, b, k, P, s, W))) return rc;
+    if (W.ws != W.ms) { /* window stage -> emit */
         hipEvent_t e = sev_get(c);
         if (!e) return fail(c, NTL_EDEVICE, "hipEventCreate failed");
-        HIPCHK(c, hipEventRecord(e, ws));
-        HIPCHK(c, hipStreamWaitEvent(ms, e, 0));
+        HIPCHK(c, hipEventRecord(e, W.ws));
+        HIPCHK(c, hipStreamWaitEvent(W.ms, e, 0));
         sev_put(c, e); /* the wait holds what it needs; the handle may be recorded again */
     }
-    {
-        ProfSpan sp(c, "sketch_emit");
-        const uint64_t tiles = lists ? (ub_strips + EL_STRIPS - 1) / EL_STRIPS : (nmask + EMIT_TILE - 1) / EMIT_TILE;
-        DevBuf tile_seq, tile_next;
-        if ((rc = tile_next.alloc(c, 8 * 16 * 4))) return rc;
-        if (lists) {
-            /* ranks: a scan over one count per strip; the total (or, if the lists ran out of pool, a total no array holds: the map
-               kernels leave such a sketch alone and sketch_finalize makes it again through the bitmask) */
-            strip_first.touch(SID_MAIN); strip_tab.touch(SID_MAIN);
-            if ((rc = device_scan(c, Ls.cnt, loff.as<uint32_t>(), ub_strips, nullptr, 1, &dsums->total_mx))) return rc;
-            SketchSums *hd = (SketchSums *)slot_dev(c, s->slot); /* the true total and whether the lists ran out, for the host */
-            hipLaunchKernelGGL(list_fail_kernel, dim3(1), dim3(64), 0, ms, (const uint32_t *)Ls.ctl, &dsums->total_mx, &dsums->list_fail, tile_next.as<uint32_t>(),
-                               &hd->total_mx, &hd->list_fail);
-            hipLaunchKernelGGL(mx_off_from_strips_kernel, dim3((unsigned)((nseq + 256) / 256)), dim3(256), 0, ms, (const uint32_t *)strip_first.as<uint32_t>(),
-                               (const uint32_t *)loff.as<uint32_t>(), (uint32_t)nseq, s->mx_off.as<uint32_t>());
-        } else {
-            if ((rc = tile.alloc(c, tiles * 4)) || (rc = tile_seq.alloc(c, (tiles + 2) * 4))) return rc;
-            if (nseq)
-                hipLaunchKernelGGL(tile_seq_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, ms, (const uint64_t *)T.seq_base, (uint32_t)nseq,
-                                   tiles, tile_seq.as<uint32_t>());
-            hipLaunchKernelGGL(mask_count_kernel, dim3((unsigned)tiles), dim3(EMIT_NT), 0, ms,
-                               (const uint32_t *)mask.p, nmask, tile.as<uint32_t>(), tile_next.as<uint32_t>());
-            hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(SCAN_NT), 0, ms, tile.as<uint32_t>(), tiles, &dsums->total_mx, (uint64_t)0, (uint32_t *)nullptr);
-        }
-        HIPCHK(c, hipGetLastError());
-        if (!s->no_records && (rc = s->records.alloc(c, cap * sizeof(MxRecord)))) return rc;
-        if (ix && (rc = s->rpos.alloc(c, cap * 4))) return rc;
-        s->cap = cap;
-        const int probe = !ix ? 0 : (ix->hit_fraction->load(std::memory_order_relaxed) <= 0.5f ? 1 : 2); /* tags first unless the last batch on this index mostly hit */
-        if (ix) {
-            if ((rc = s->cand.alloc(c, cap * sizeof(Cand)))) return rc;
-            s->cand_gen = ix->gen;
-            if (ix->c != c && ix->built) HIPCHK(c, hipStreamWaitEvent(ms, ix->built, 0));
-        }
-        EmitArgs E;
-        E.packed = T.packed; E.seq_base = T.seq_base; E.nseq = (uint32_t)nseq; E.mask = (uint32_t *)mask.p;
-        E.nwords = nmask; E.tile_off = tile.as<uint32_t>(); E.tile_seq = tile_seq.as<uint32_t>(); E.mx_off = s->mx_off.as<uint32_t>();
-        E.out = s->no_records ? nullptr : s->records.as<MxRecord>(); E.out_cap = (uint32_t)cap;
-        E.k = k; E.mult = 1ull ^ ((uint64_t)k * 0x90b45d39fb6da1faull);
-        uint64_t roll[16][2];
-        make_tables(k, roll, E.seed_tab);
-        E.g4 = (const uint64_t (*)[2])c->g4;
-        E.g8 = (const uint64_t (*)[2])c->g8;
-        E.slots = nullptr; E.tags = nullptr; E.special = nullptr; E.ix_bits = 0; E.cand = nullptr; E.nfound = nullptr;
-        E.rpos = ix ? s->rpos.as<uint32_t>() : nullptr;
-        if (ix) {
-            E.slots = ix->slots.as<IndexSlot>(); E.tags = ix->tags.as<uint8_t>(); E.special = ix->special.as<IndexSpecial>();
-            E.ix_bits = ix->bits; E.cand = s->cand.as<Cand>(); E.nfound = &dsums->nfound;
-        }
-        /* the emit kernel is the last reader of the bitmask and clears the words it read: the mask goes back clean */
-        /* Beside the window stage (two streams) the emit kernel may keep to a bounded number of resident workgroups that take
-           their tiles from counters; alone: one workgroup per tile, as many resident as fit. */
-        E.ntiles = (uint32_t)tiles; E.tile_next = nullptr;
-        unsigned egrid = (unsigned)tiles;
-        {
-            /* the direct-slot form (most lookups hit: one random 64-byte line from HBM per minimizer) is bound by the rate of those
-               transactions and gains nothing beyond 12 wavefronts per CU, while the slots it holds are missed by the map kernels
-               and the window stage: C5 296-300 -> 269-271 ms per step at 3 workgroups per CU, 275 at 5, 280 at 4 with other window
-               grids (profiles/r04_share_sweep_C5.jsonl); the tag form (C3) is as fast uncapped (74.4-75.0 against 74.9-75.9) */
-            /* emit_list_kernel (44 registers, 13 KB of LDS) would fill all 32 wavefront slots of a CU, and the window stage's resident
-               workgroups of the next sub-batch then wait for them to drain (C3: 91 ms per step uncapped, 75.9 at two per CU) */
-            /* beside the DENSE window shapes (w < 137: twelve window wavefronts per CU, window_plan) the tag form takes four: C2
-               0.890 -> 0.800 ms per step (0.806 at three, 0.815 uncapped; profiles/r07b_C2_share_sweep.txt) */
-            int per_cu = !c->pipelined ? 0 : (probe == 2 ? 3 : (lists ? (P.dense_windows ? 4 : 2) : 0));
-            if (const char *e = getenv("NTL_EMIT_WGS_PER_CU")) per_cu = atoi(e);
-            const uint64_t cap = (uint64_t)per_cu * (uint64_t)c->n_cu;
-            if (per_cu > 0 && cap >= 8 && cap < tiles) { egrid = (unsigned)cap; E.tile_next = tile_next.as<uint32_t>(); }
-            else if (per_cu < 0) { egrid = (unsigned)(-per_cu < 8 ? 8 : -per_cu); E.tile_next = tile_next.as<uint32_t>(); } /* tests: that many workgroups whatever the size */
-        }
-        const char *eu = getenv("NTL_EMIT_U"); /* minimizers in flight per thread; read per call: the tests switch it inside one process */
-        const int emit_u = eu ? atoi(eu) : 1;
-        if (lists) {
-            EmitListArgs Q;
-            Q.Ls = Ls; Q.strip_tab = strip_tab.as<StripInfo>(); Q.strip_off = loff.as<uint32_t>(); Q.nstrips = (uint32_t)ub_strips;
-            if (probe == 0) hipLaunchKernelGGL((emit_list_kernel<0, 1>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
-            else if (probe == 1 && emit_u >= 4) hipLaunchKernelGGL((emit_list_kernel<1, 4>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
-            else if (probe == 1 && emit_u >= 2) hipLaunchKernelGGL((emit_list_kernel<1, 2>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
-            else if (probe == 1) hipLaunchKernelGGL((emit_list_kernel<1, 1>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
-            else if (emit_u >= 4) hipLaunchKernelGGL((emit_list_kernel<2, 4>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
-            else if (emit_u >= 2) hipLaunchKernelGGL((emit_list_kernel<2, 2>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
-            else hipLaunchKernelGGL((emit_list_kernel<2, 1>), dim3(egrid), dim3(EL_NT), 0, ms, E, Q);
-        } else
-        if (probe == 0 && (eu ? emit_u >= 4 : P.pass == WP_SMALL)) hipLaunchKernelGGL((emit_kernel<0, 4, NTL_EMIT_DENSE_CAP>), dim3(egrid), dim3(EMIT_NT), 0, ms, E); /* dense sketches: rounds of 8192, four k-mers' loads in flight per thread */
-        else if (probe == 0 && emit_u >= 2) hipLaunchKernelGGL((emit_kernel<0, 2>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
-        else if (probe == 0) hipLaunchKernelGGL((emit_kernel<0, 1>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
-        else if (probe == 1 && emit_u >= 2) hipLaunchKernelGGL((emit_kernel<1, 2>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
-        else if (probe == 1) hipLaunchKernelGGL((emit_kernel<1, 1>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
-        else if (emit_u >= 2) hipLaunchKernelGGL((emit_kernel<2, 2>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
-        else hipLaunchKernelGGL((emit_kernel<2, 1>), dim3(egrid), dim3(EMIT_NT), 0, ms, E);
-        HIPCHK(c, hipGetLastError());
-        if (mask.p) {
-            mask.clean = sev_get(c);
-            if (mask.clean) HIPCHK(c, hipEventRecord(mask.clean, ms));
-            else HIPCHK(c, hipStreamSynchronize(ms));
-            c->masks.push_back(mask);
-            mask.p = nullptr; /* handed over */
-        }
-        /* (the map kernels read the lengths of the sketched sequences from the batch itself: ntl_map_run holds it) */
-        s->nfound_owed = false;
-        if (!lists) { /* the bitmask path (off the hot path): the totals come back by copies */
-            SketchSums *hs = (SketchSums *)s->slot;
-            HIPCHK(c, hipMemcpyAsync(&hs->total_mx, &dsums->total_mx, 4, hipMemcpyDeviceToHost, ms));
-            if (ix) HIPCHK(c, hipMemcpyAsync(&hs->nfound, &dsums->nfound, 8, hipMemcpyDeviceToHost, ms));
-        } else s->nfound_owed = ix != nullptr; /* (list_fail_kernel wrote the total and the flag) */
-    }
-    HIPCHK(c, hipEventRecord(s->done, ms));
-    {
-        hipEvent_t &t = c->throttle[c->n_enqueued & 7u];
-        if (!t) t = sev_get(c);
-        if (t) HIPCHK(c, hipEventRecord(t, ms));
-        c->n_enqueued++;
-    }
-    s->strips = ub_strips;
-    s->from_lists = lists;
-    {   /* the plan that was carried out, as plain integers (ntl_sketch_plan) */
-        ntl_plan_info &I = s->plan;
-        memset(&I, 0, sizeof I);
-        I.pass = (int32_t)P.pass; I.nt = P.nt; I.C = P.C; I.NWO = G.NWO;
-        I.big = P.big; I.direct = P.direct; I.lists = P.lists; I.thresh = P.thresh;
-        if (P.pass == WP_WAVE) wave_shape_numbers(P.shape, &I.wave_wavefronts);
-    }
+    if ((rc = sketch_emit_stage(c, b, k, P, ix, s, cap, W))) return rc;
+    HIPCHK(c, hipEventRecord(s->done, W.ms));
+    if (!throttle) throttle = sev_get(c);
+    if (throttle) HIPCHK(c, hipEventRecord(throttle, W.ms));
+    c->n_enqueued++;
+    s->strips = P.strips; s->from_lists = P.lists;
+    ntl_plan_info &I = s->plan; /* the plan that was carried out, as plain integers (ntl_sketch_plan) */
+    memset(&I, 0, sizeof I);
+    I.pass = (int32_t)P.pass; I.nt = P.nt; I.C = P.C; I.NWO = P.G.NWO;
+    I.big = P.big; I.direct = P.direct; I.lists = P.lists; I.thresh = P.thresh;
+    if (P.pass == WP_WAVE) wave_shape_numbers(P.shape, &I.wave_wavefronts);
     s->pending = true;
-    /* temporaries return to the context's cache here; every later user of those blocks is queued behind the kernels above
-       on the stream they were used on, so no wait is needed */
-    return NTL_OK;
+    return NTL_OK; /* (W's temporaries return to the context's cache here) */
 }
 
 static int sketch_run_impl(ntl_ctx *c, const ntl_batch *b, int k, int w, const ntl_index *ix, ntl_sketch **out, bool no_records = false)

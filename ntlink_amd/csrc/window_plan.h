@@ -1,6 +1,7 @@
 /*
  * The plan of a sketch's window pass: what window_plan() (ntl_hip.hip) decides once per sketch, before anything is allocated or
- * launched, and launch_window_pass() and the emit stage of sketch_enqueue() carry out.
+ * launched, and sketch_enqueue()'s stages carry out: launch_window_pass() in sketch_window_stage(), and sketch_emit_stage() with
+ * emit_grid() and emit_launch().
  */
 #pragma once
 #include "sketch2_kernels.h"

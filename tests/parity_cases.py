@@ -590,3 +590,64 @@ def check_strip_lists(dev, monkeypatch, scale=1):
         m.setenv("NTL_SKETCH_LISTS", "0")
         assert check_sketch(dev, seqs, 32, 250, info=info) > 0 and not info["from_lists"]
     assert check_sketch(dev, seqs, 32, 64, info=info) > 0 and not info["from_lists"]  # (a window of the bitmask passes)
+
+
+def _write_fasta(path, seqs):
+    with open(path, "wb") as fh:
+        for i, s in enumerate(seqs):
+            fh.write(b">c%d\n" % i + s + b"\n")
+    return str(path)
+
+
+def _three_batches(dev, path, nseq):
+    """The records of a FASTA file as device batches made by ntl_batch_create (ASCII), ntl_batch_create_packed (the two-pass packing
+    reader) and ntl_batch_create_packed_at (the one-pass reader).  The readers yield nothing for a file without records: those
+    two sets are then written out by hand, as the readers lay out a set of no sequences."""
+    from ntlink_amd import seqio
+    ascii_ss = seqio.load_all([path])
+    if nseq:
+        packed_ss = seqio.load_all([path], packed=True)
+        at_ss, = seqio.load([path], max_bases=1 << 20, packed=True)
+    else:
+        none = dict(packed=np.zeros(int(capi.load().ntl_packed_words(0)), np.uint32), runs=(np.zeros(1, np.uint32), np.zeros(0, np.uint32), np.zeros(0, np.uint32)))
+        packed_ss = seqio.SeqSet([], None, np.zeros(1, np.uint64), **none)
+        at_ss = seqio.SeqSet([], None, np.zeros(1, np.uint64), positions=np.zeros(0, np.uint64), span_positions=0, **none)
+    assert len(ascii_ss) == len(packed_ss) == len(at_ss) == nseq
+    assert packed_ss.packed is not None and packed_ss.positions is None and at_ss.positions is not None
+    return [dev.batch(ascii_ss.buf, ascii_ss.offsets), dev.batch_packed(packed_ss), dev.batch_packed(at_ss)]
+
+
+def _download_outcome(batch):
+    try:
+        buf, off = batch.download()
+        return buf.tobytes(), off.tolist()
+    except capi.NtlError as e:
+        return str(e)
+
+
+def check_batch_constructors(dev, tmp_path):
+    """The three batch constructors share one layout: an empty record, a record of two ACGT runs, a pure-ACGT one and one that ends
+    in N -- Batch.download() answers the same for all three forms (it refuses a batch with N in it, and a batch of the pure-ACGT
+    record alone comes back as it went in), the sketches at (k, w) = (8, 3) and (15, 16) are identical and the oracle's; a file
+    without records gives an empty sketch in every form."""
+    rng = np.random.default_rng(31)
+    seqs = [b"", random_bases(rng, 18) + b"NNNN" + random_bases(rng, 18), random_bases(rng, 100), random_bases(rng, 32) + b"N"]
+    assert [len(s) for s in seqs] == [0, 40, 100, 33]
+    for name, recs in (("four.fa", seqs), ("pure.fa", seqs[2:3]), ("none.fa", [])):
+        batches = _three_batches(dev, _write_fasta(tmp_path / name, recs), len(recs))
+        outcomes = [_download_outcome(b) for b in batches]
+        assert outcomes[0] == outcomes[1] == outcomes[2], name
+        if name == "pure.fa":
+            assert outcomes[0] == (recs[0], [0, 100])
+        elif name == "four.fa":
+            assert "pure-ACGT" in outcomes[0]
+        for k, w in ((8, 3), (15, 16)):
+            want = oracle.sketch_batch(b"".join(recs), offsets_of(recs), k, w)
+            for b in batches:
+                assert (b.nseq, b.bases) == (len(recs), sum(map(len, recs)))
+                with dev.sketch(b, k, w) as sk:
+                    got, count = sk.download(), sk.count
+                assert all(np.array_equal(g, o) for g, o in zip(got, want)), (name, k, w)
+                assert count == len(got[1]) and (recs or count == 0)
+        for b in batches:
+            b.close()

@@ -192,17 +192,30 @@ def _function_body(src, name):
         j += 1
 
 
+# the stages sketch_enqueue is split into (mask_take, device_scan and launch_window_pass were separate before and stay out)
+SKETCH_STAGES = ["sketch_prepare", "g8k_for", "sketch_window_stage", "emit_grid", "emit_launch", "sketch_emit_stage"]
+
+
 def test_hot_path_queues_no_copies_or_fills():
     """The calls of the hot path (a read sketch made for an index, then its map) put no copy and no fill on a stream: the sizes and sums
-    reach the host through the slots, written by the kernels.  What is left in sketch_enqueue belongs to the bitmask path (its totals)
-    and to a batch without sequences."""
+    reach the host through the slots, written by the kernels.  What is left in sketch_enqueue and its stages belongs to the bitmask
+    path (its totals) and to a batch without sequences."""
     src = open(os.path.join(ROOT, "ntlink_amd", "csrc", "ntl_hip.hip")).read()
     ops = re.compile(r"hip(?:Memcpy|Memset)(?:Async|D2D|D2H|H2D)?\s*\(")
     assert not ops.findall(_function_body(src, "map_enqueue"))
-    body = _function_body(src, "sketch_enqueue")
+    top = _function_body(src, "sketch_enqueue")
+    stages = {name: _function_body(src, name) for name in SKETCH_STAGES}  # (asserts that each is found)
+    body = top + "".join(stages.values())
+    for name in ("sketch_prepare", "sketch_window_stage", "sketch_emit_stage"):  # sketch_enqueue itself calls the three stages,
+        assert re.search(r"\b" + name + r"\(", top), name
+    for name in SKETCH_STAGES:  # and every helper is called by it or by one of them: nothing is listed that the hot path does not run
+        assert re.search(r"\b" + name + r"\(", body.replace(stages[name], "")), name
     left = [body[m.start():body.index(";", m.start())] for m in ops.finditer(body)]
     assert len(left) == 3, left
     assert "if (!nseq) HIPCHK(c, hipMemsetAsync(dsums" in body
-    bitmask = body[body.index("if (!lists) { /* the bitmask path"):]
+    marker = "if (!lists) { /* the bitmask path"
+    assert body.count(marker) == 1
+    holder, = [b for b in [top, *stages.values()] if marker in b]
+    bitmask = holder[holder.index(marker):]
     assert sum(1 for m in ops.finditer(bitmask)) == 2
     assert "redo.p, 8, hipMemcpyDeviceToHost" not in body

@@ -351,6 +351,12 @@ def test_strip_lists(dev, monkeypatch):
     pc.check_strip_lists(dev, monkeypatch, scale=40)
 
 
+def test_batch_constructors_share_one_layout(dev, tmp_path):
+    """ntl_batch_create, ntl_batch_create_packed and ntl_batch_create_packed_at on the same four records, and on a file without any
+    (parity_cases.check_batch_constructors)."""
+    pc.check_batch_constructors(dev, tmp_path)
+
+
 @pytest.mark.parametrize("name,n_reads", [("C3", 100_000), ("C5", 100_000)])
 def test_full_size_assembly_parity(dev, name, n_reads):
     """BASELINE configs[2] / configs[4] at FULL assembly size: 3 Gbp in 5000 contigs on the device (same generator as

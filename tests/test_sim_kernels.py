@@ -358,6 +358,12 @@ def test_sim_packed_batches_sketch_like_ascii_batches(dev, tmp_path):
         assert np.array_equal(off, ooff) and np.array_equal(h, oh) and np.array_equal(q, op) and np.array_equal(s, os_)
 
 
+def test_sim_batch_constructors_share_one_layout(dev, tmp_path):
+    """ntl_batch_create, ntl_batch_create_packed and ntl_batch_create_packed_at on the same four records, and on a file without any
+    (parity_cases.check_batch_constructors)."""
+    pc.check_batch_constructors(dev, tmp_path)
+
+
 def test_sim_probe_with_and_without_tags(dev):
     """probe_kernel<true> (first batch) and probe_kernel<false> (after a batch that found most minimizers): same records."""
     rng = np.random.default_rng(12)
