@@ -1,7 +1,8 @@
 /*
  * Host side of libntlink_hip.so: the C ABI of include/ntlink_amd.h over the HIP kernels.
- * One context = one device + one stream; all launches are asynchronous on that stream and the
- * host only synchronises where a size has to come back (totals of the offset scans).
+ * One context = one device + two streams (MAIN, and the window stage's unless NTL_PIPELINE=0) + the device block allocator
+ * (dev_pool.h).  All launches are asynchronous; the host waits only where a caller asks for a count or a record of a handle that
+ * the device has not finished yet.
  */
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -22,6 +23,7 @@
 
 #include "../../include/ntlink_amd.h"
 #include "dev_common.h"
+#include "dev_pool.h"
 #include "scan_kernels.h"
 #include "sketch_kernels.h"
 #include "sketch2_kernels.h"
@@ -51,17 +53,13 @@
  * removed: the step got longer (profiles/HISTORY.md, profiles/r04_prep_stream.jsonl); those kernels run on the window stream.
  */
 enum { SID_MAIN = 0, SID_W = 1, NTL_NSID = 2 };
+static_assert(SID_MAIN == DevPool::MAIN && SID_W == DevPool::WINDOW && NTL_NSID == DevPool::NSID, "the pool's stream ids are the context's");
+static_assert(NTL_OK == DevPool::OK && NTL_ENOMEM == DevPool::NOMEM, "the pool's return codes are the C ABI's");
 
 struct ProfEntry {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> spans;
     double done_ms = 0;
     uint64_t launches = 0;
-};
-
-/* a cached device block that was used on both streams: whoever takes it waits for the events of the streams it is not on */
-struct XBlock {
-    void *p = nullptr;
-    hipEvent_t ev[NTL_NSID] = {}; /* nullptr: not used on that stream */
 };
 
 /* a zero-filled minimizer bitmask whose last reader (emit_kernel) cleared what the window stage had set */
@@ -103,25 +101,7 @@ struct ntl_ctx {
     void *g4 = nullptr;                 /* device copy of the four-base init table */
     void *g8 = nullptr;                 /* device copy of the eight-base init table (1 MB) */
     std::map<int, void *> g8k;          /* k -> the two k-dependent ring forms of g8 the fast window pass reads (1 MB per k, sketch2_kernels.h) */
-    std::multimap<size_t, void *> pool[NTL_NSID]; /* cached device blocks by size, per stream they were last used on */
-    std::multimap<size_t, XBlock> xpool;   /* ... and those that were used on both */
-    size_t pool_bytes = 0;
-    size_t pool_cap = (size_t)32 << 30; /* upper bound of pool_bytes */
-    /* Blocks up to NTL_SLAB_MAX_REQ are cut from slabs of NTL_SLAB_BYTES (a bump pointer; the cache above recycles them): a
-       hipMalloc costs 4-9 ms of host time whatever its size, and a context's first read batch asked for seventy of them -- 0.6 s
-       per context of a process's first pass (profiles/r04_first_pass.txt).  A slab block that the cache drops goes onto the slabs'
-       free list (by size) and is handed out again; a slab without a live block goes back to the driver when memory runs out
-       (dev_alloc), so the bound of the cache bounds the slabs too (round 5). */
-    struct Slab { char *base; size_t size; size_t live; };
-    std::vector<Slab> slabs;
-    std::multimap<size_t, void *> slab_free;   /* dropped slab blocks by size */
-    std::unordered_map<void *, size_t> slab_size; /* every slab block's TRUE size (a reused block may be up to 25 % larger than what was asked for; round 6) */
-    /* slab blocks that were given back while work on them may still be queued: they join slab_free when the events recorded behind that
-       work have passed (polled by dev_alloc) -- no stream is waited for (round 6, ADVICE r5: dev_free used to synchronise them) */
-    struct Limbo { void *p; size_t bytes; hipEvent_t ev[NTL_NSID]; };
-    std::deque<Limbo> slab_limbo;
-    char *slab_cur = nullptr, *slab_end = nullptr;
-    std::mutex slab_mu; /* (dev_free may be asked about another context's block: index_unref) */
+    DevPool mem;                        /* every device block of the context but the tables above (dev_pool.h) */
     std::deque<CleanMask> masks;
     void *host_tmp = nullptr;           /* page-locked bounce buffer for record downloads (grows, never shrinks) */
     size_t host_tmp_cap = 0;
@@ -311,183 +291,8 @@ static PinSlot *slot_get(ntl_ctx *c)
     return p;
 }
 
-#define NTL_SLAB_BYTES ((size_t)1 << 30)
-#define NTL_SLAB_MAX_REQ ((size_t)192 << 20)
-
-static hipError_t sync_both(ntl_ctx *c);
-
-/* the slab a block lies in (slab_mu held), or NULL */
-static ntl_ctx::Slab *slab_of(ntl_ctx *c, const void *p)
-{
-    for (auto &sl : c->slabs)
-        if ((const char *)p >= sl.base && (const char *)p < sl.base + sl.size) return &sl;
-    return nullptr;
-}
-
-static void slab_limbo_poll(ntl_ctx *c, bool wait); /* (slab_mu held) */
-
-/* Gives a block of dev_alloc (of `bytes`, as asked for there) back.  A single block: hipFree.  A slab block is not waited for: an
-   event is recorded behind each of the context's streams and the block goes into limbo; it joins the slabs' free list when the
-   events have passed (slab_limbo_poll).  slab_mu is held around the slabs' bookkeeping only, never across a call that may wait. */
-static void dev_free(ntl_ctx *c, void *p, size_t bytes)
-{
-    if (!p) return;
-    ntl_ctx::Limbo L = {};
-    {
-        std::lock_guard<std::mutex> g(c->slab_mu);
-        if (slab_of(c, p)) {
-            L.p = p;
-            auto ts = c->slab_size.find(p);
-            L.bytes = ts != c->slab_size.end() ? ts->second : ((bytes + 255) & ~(size_t)255);
-        }
-    }
-    if (!L.p) { (void)hipFree(p); return; }
-    /* what is still queued on the block: an event behind each of the context's streams (made here, not taken from the context's event
-       list: this may be another context's thread, index_unref); no event to be had: the slow, safe way */
-    hipStream_t st[NTL_NSID] = {c->stream, c->wstream != c->stream ? c->wstream : nullptr};
-    bool ok = true;
-    for (int i = 0; i < NTL_NSID && ok; i++)
-        if (st[i]) ok = hipEventCreateWithFlags(&L.ev[i], hipEventDisableTiming) == hipSuccess && hipEventRecord(L.ev[i], st[i]) == hipSuccess;
-    if (!ok) {
-        (void)hipGetLastError();
-        for (int i = 0; i < NTL_NSID; i++) if (L.ev[i]) { (void)hipEventDestroy(L.ev[i]); L.ev[i] = nullptr; }
-        (void)sync_both(c);
-    }
-    /* (the slab is looked up again: dev_alloc may have added one meanwhile; this block's own slab stays, it still counts as live) */
-    std::lock_guard<std::mutex> g(c->slab_mu);
-    ntl_ctx::Slab *sl = slab_of(c, p);
-    if (sl && sl->live) sl->live--;
-    c->slab_limbo.push_back(L);
-    slab_limbo_poll(c, false);
-}
-
-/* limbo blocks whose events have passed go onto the free list (wait: all of them, after waiting) */
-static void slab_limbo_poll(ntl_ctx *c, bool wait)
-{
-    for (auto it = c->slab_limbo.begin(); it != c->slab_limbo.end();) {
-        bool done = true;
-        for (int i = 0; i < NTL_NSID && done; i++)
-            if (it->ev[i]) {
-                hipError_t q = wait ? hipEventSynchronize(it->ev[i]) : hipEventQuery(it->ev[i]);
-                if (q == hipErrorNotReady) done = false;
-            }
-        if (!done) { ++it; continue; }
-        (void)hipGetLastError();
-        for (int i = 0; i < NTL_NSID; i++) if (it->ev[i]) (void)hipEventDestroy(it->ev[i]);
-        c->slab_free.insert({it->bytes, it->p});
-        it = c->slab_limbo.erase(it);
-    }
-    (void)hipGetLastError(); /* (hipErrorNotReady is not an error) */
-}
-
-/* slabs without a live block go back to the driver (out of memory: dev_alloc); returns the bytes freed */
-static size_t slabs_trim(ntl_ctx *c)
-{
-    std::lock_guard<std::mutex> g(c->slab_mu);
-    slab_limbo_poll(c, true); /* (memory has run out: wait for what is in limbo, its slabs may go) */
-    size_t freed = 0;
-    for (size_t i = 0; i < c->slabs.size();) {
-        ntl_ctx::Slab sl = c->slabs[i];
-        if (sl.live) { i++; continue; }
-        for (auto it = c->slab_free.begin(); it != c->slab_free.end();)
-            it = ((char *)it->second >= sl.base && (char *)it->second < sl.base + sl.size) ? c->slab_free.erase(it) : std::next(it);
-        if (c->slab_cur >= sl.base && c->slab_cur <= sl.base + sl.size) c->slab_cur = c->slab_end = nullptr;
-        for (auto it = c->slab_size.begin(); it != c->slab_size.end();)
-            it = ((char *)it->first >= sl.base && (char *)it->first < sl.base + sl.size) ? c->slab_size.erase(it) : std::next(it);
-        (void)hipFree(sl.base);
-        freed += sl.size;
-        c->slabs.erase(c->slabs.begin() + (long)i);
-    }
-    return freed;
-}
-
-static void pool_drop_all(ntl_ctx *c)
-{
-    for (int i = 0; i < NTL_NSID; i++) {
-        for (auto &kv : c->pool[i]) dev_free(c, kv.second, kv.first);
-        c->pool[i].clear();
-    }
-    for (auto &kv : c->xpool) {
-        dev_free(c, kv.second.p, kv.first);
-        for (int o = 0; o < NTL_NSID; o++) sev_put(c, kv.second.ev[o]);
-    }
-    c->xpool.clear();
-    c->pool_bytes = 0;
-}
-
-static const bool g_pool_trace = getenv("NTL_POOL_TRACE") != nullptr; /* diagnostics: every hipMalloc / hipFree of the block cache on stderr */
-
-static int dev_alloc(ntl_ctx *c, size_t bytes, void **out)
-{
-#ifdef NTL_SIM
-    static const bool use_slabs = false; /* the mock's blocks stay single allocations: the CPU sanitizers see every array's ends */
-#else
-    static const bool use_slabs = [] { const char *e = getenv("NTL_SLABS"); return !e || atoi(e) != 0; }();
-#endif
-    if (use_slabs && bytes <= NTL_SLAB_MAX_REQ) {
-        const size_t need = (bytes + 255) & ~(size_t)255;
-        {   /* a dropped slab block of this size (whatever was queued on it has run: slab_limbo_poll) */
-            std::lock_guard<std::mutex> g(c->slab_mu);
-            if (!c->slab_limbo.empty()) slab_limbo_poll(c, false);
-            auto it = c->slab_free.lower_bound(need);
-            if (it != c->slab_free.end() && it->first <= need + need / 4) {
-                *out = it->second;
-                if (ntl_ctx::Slab *sl = slab_of(c, it->second)) sl->live++;
-                c->slab_free.erase(it);
-                return NTL_OK;
-            }
-        }
-        if (!c->slab_cur || (size_t)(c->slab_end - c->slab_cur) < need) {
-            void *sl = nullptr;
-            const auto ts = std::chrono::steady_clock::now();
-            if (hipMalloc(&sl, NTL_SLAB_BYTES) == hipSuccess) {
-                ProfEntry &pe = c->profs["hipMalloc"];
-                pe.done_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - ts).count();
-                pe.launches++;
-                std::lock_guard<std::mutex> g(c->slab_mu);
-                /* what is left of the slab before it, as a free block (else it would be lost while one of its blocks lives) */
-                if (c->slab_cur && c->slab_end - c->slab_cur >= 256) {
-                    c->slab_free.insert({(size_t)(c->slab_end - c->slab_cur) & ~(size_t)255, c->slab_cur});
-                    c->slab_size[c->slab_cur] = (size_t)(c->slab_end - c->slab_cur) & ~(size_t)255;
-                }
-                c->slabs.push_back({(char *)sl, NTL_SLAB_BYTES, 0});
-                c->slab_cur = (char *)sl; c->slab_end = (char *)sl + NTL_SLAB_BYTES;
-            } else (void)hipGetLastError(); /* no room for a slab: single blocks as before */
-        }
-        if (c->slab_cur && (size_t)(c->slab_end - c->slab_cur) >= need) {
-            std::lock_guard<std::mutex> g(c->slab_mu);
-            *out = c->slab_cur;
-            c->slab_size[c->slab_cur] = need;
-            if (ntl_ctx::Slab *sl = slab_of(c, c->slab_cur)) sl->live++;
-            c->slab_cur += need;
-            return NTL_OK;
-        }
-    }
-    const auto t0 = std::chrono::steady_clock::now();
-    hipError_t e = hipMalloc(out, bytes);
-    {   /* host time of the block cache's misses: ntl_prof_get(ctx, "hipMalloc") -- what a process's first pass pays once */
-        ProfEntry &pe = c->profs["hipMalloc"];
-        pe.done_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        pe.launches++;
-    }
-    if (g_pool_trace)
-        fprintf(stderr, "ntl pool: hipMalloc %.1f MB -> %s in %.3f ms (cached %.1f MB of %.1f)\n", bytes / 1e6, e == hipSuccess ? "ok" : "FAILED",
-                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(), c->pool_bytes / 1e6, c->pool_cap / 1e6);
-    if (e != hipSuccess) {
-        /* drop the cache -- single blocks go back to the driver, slab blocks to their free list and the slabs that hold nothing
-           else to the driver -- and retry once */
-        pool_drop_all(c);
-        (void)slabs_trim(c);
-        e = hipMalloc(out, bytes);
-        if (e != hipSuccess) return fail(c, NTL_ENOMEM, "hipMalloc failed");
-    }
-    return NTL_OK;
-}
-
-/* A device buffer that returns to the context's cache.  The cache is stream-ordered: a block goes back while kernels that
- * use it may still be queued, and is handed out again to work queued BEHIND them on the same stream (no wait).  A block that
- * was used on both streams (touch) goes back with an event per stream, and whoever takes it next waits for the other
- * stream's. */
+/* A device buffer that returns to the context's block cache (dev_pool.h): the RAII handle over take / give.  touch() notes a second
+ * stream that work on the buffer is queued on. */
 struct DevBuf {
     ntl_ctx *c = nullptr;
     void *p = nullptr;
@@ -501,97 +306,14 @@ struct DevBuf {
         release();
         c = ctx;
         sid = c->sid(sid);
+        if (c->mem.take(n, sid, &p, &bytes) != DevPool::OK) { p = nullptr; bytes = 0; return fail(c, NTL_ENOMEM, "hipMalloc failed"); }
         used = (uint8_t)(1u << sid);
-        size_t want = n ? n : 256;
-        want = (want + 255) & ~(size_t)255;
-        /* Size classes (32 per power of two, at most 3 % over the request): consecutive read batches ask for arrays whose
-           sizes differ in the fourth digit, and a cached block a hair smaller than the request is useless -- without classes
-           every batch allocated its largest arrays anew while the cache filled with near-misses up to its bound and then
-           evicted (hipFree: a device-wide wait) exactly the blocks the next batch wanted (C5: 2.6 s per step instead of 0.45). */
-        if (want >= ((size_t)1 << 20)) {
-            size_t step = (size_t)1 << 15;
-            while ((step << 6) <= want) step <<= 1; /* step = 2^(floor(log2 want) - 5) */
-            want = (want + step - 1) & ~(step - 1);
-        }
-        const size_t most = want + want / 4 + (1 << 20);
-        /* look for a cached block; its true size is the map key */
-        auto it = c->pool[sid].lower_bound(want);
-        if (it != c->pool[sid].end() && it->first <= most) {
-            p = it->second; bytes = it->first;
-            c->pool_bytes -= it->first;
-            c->pool[sid].erase(it);
-            return NTL_OK;
-        }
-        /* A block that was used on several streams: one whose work on the OTHER streams has run by now is taken as it is; else a
-           new block is made rather than this stream made to wait (two or three blocks per size then go round);
-           only when no memory is to be had does the taker wait. */
-        auto first = c->xpool.lower_bound(want), pick = c->xpool.end();
-        for (auto xt = first; xt != c->xpool.end() && xt->first <= most; ++xt) {
-            bool ready = true;
-            for (int o = 0; o < NTL_NSID; o++)
-                if (o != sid && xt->second.ev[o] && hipEventQuery(xt->second.ev[o]) != hipSuccess) { ready = false; break; }
-            if (ready) { pick = xt; break; }
-        }
-        (void)hipGetLastError(); /* (hipErrorNotReady is not an error) */
-        int rc = NTL_OK;
-        if (pick == c->xpool.end()) {
-            rc = dev_alloc(c, want, &p);
-            if (rc == NTL_OK) { bytes = want; return NTL_OK; }
-            p = nullptr;
-            if (first == c->xpool.end() || first->first > most) return rc;
-            pick = first; /* out of memory: the oldest candidate, and a wait */
-            c->err.clear();
-        }
-        XBlock &x = pick->second;
-        for (int o = 0; o < NTL_NSID; o++) {
-            if (o != sid && x.ev[o]) (void)hipStreamWaitEvent(c->s(sid), x.ev[o], 0);
-            sev_put(c, x.ev[o]);
-        }
-        p = x.p; bytes = pick->first;
-        c->pool_bytes -= pick->first;
-        c->xpool.erase(pick);
         return NTL_OK;
     }
     void touch(int sid) const { if (c) used |= (uint8_t)(1u << c->sid(sid)); }
     void release()
     {
-        if (p && c) {
-            const bool on_main = used & (1u << SID_MAIN), on_w = used & (1u << SID_W);
-            if (on_main != on_w) c->pool[on_w ? SID_W : SID_MAIN].insert({bytes, p}); /* one stream: its own cache */
-            else {
-                XBlock x;
-                x.p = p;
-                for (int o = 0; o < NTL_NSID; o++) {
-                    if (!(used & (1u << o))) continue;
-                    x.ev[o] = sev_get(c);
-                    if (x.ev[o]) (void)hipEventRecord(x.ev[o], c->s(o));
-                    else (void)hipStreamSynchronize(c->s(o)); /* no event to be had: the slow, safe way */
-                }
-                c->xpool.insert({bytes, x});
-            }
-            c->pool_bytes += bytes;
-            /* the cache is bounded (half of the device memory unless NTL_POOL_MAX_BYTES says otherwise; a bound below the
-               working set of a batch -- tens of GB for 4-Gbases HiFi batches -- turns every release into a hipFree): the
-               largest blocks go first, they are the least likely to be asked for again at exactly their size */
-            while (c->pool_bytes > c->pool_cap) {
-                std::multimap<size_t, void *> *big = nullptr;
-                for (int i = 0; i < NTL_NSID; i++)
-                    if (!c->pool[i].empty() && (!big || std::prev(c->pool[i].end())->first > std::prev(big->end())->first)) big = &c->pool[i];
-                if (big && (c->xpool.empty() || std::prev(big->end())->first >= std::prev(c->xpool.end())->first)) {
-                    auto it = std::prev(big->end());
-                    if (g_pool_trace) fprintf(stderr, "ntl pool: over the bound, hipFree %.1f MB\n", it->first / 1e6);
-                    dev_free(c, it->second, it->first); /* waits for the device: safe whatever is still queued */
-                    c->pool_bytes -= it->first;
-                    big->erase(it);
-                } else if (!c->xpool.empty()) {
-                    auto it = std::prev(c->xpool.end());
-                    dev_free(c, it->second.p, it->first);
-                    for (int o = 0; o < NTL_NSID; o++) sev_put(c, it->second.ev[o]);
-                    c->pool_bytes -= it->first;
-                    c->xpool.erase(it);
-                } else break;
-            }
-        }
+        if (p && c) c->mem.give(p, bytes, used);
         p = nullptr; bytes = 0; used = 0;
     }
     ~DevBuf() { release(); }
@@ -697,8 +419,15 @@ extern "C" int ntl_ctx_create(int device, ntl_ctx **out)
     }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
-        c->pool_cap = std::max<size_t>((size_t)prop.totalGlobalMem / 2, (size_t)256 << 20);
-        if (const char *e = getenv("NTL_POOL_MAX_BYTES")) { const long long v = atoll(e); if (v >= 0) c->pool_cap = (size_t)v; }
+        size_t cache_bound = std::max<size_t>((size_t)prop.totalGlobalMem / 2, (size_t)256 << 20);
+        if (const char *e = getenv("NTL_POOL_MAX_BYTES")) { const long long v = atoll(e); if (v >= 0) cache_bound = (size_t)v; }
+#ifdef NTL_SIM
+        const bool slabs = false; /* the mock's blocks stay single allocations: the CPU sanitizers see every array's ends */
+#else
+        const char *se = getenv("NTL_SLABS");
+        const bool slabs = !se || atoi(se) != 0;
+#endif
+        c->mem.setup(c->stream, c->wstream, cache_bound, slabs);
         char buf[256];
         snprintf(buf, sizeof buf, "%s %s %d CUs %.0f GiB", prop.name, prop.gcnArchName, prop.multiProcessorCount,
                  (double)prop.totalGlobalMem / (1024.0 * 1024.0 * 1024.0));
@@ -723,17 +452,11 @@ extern "C" void ntl_ctx_destroy(ntl_ctx *c)
     (void)hipSetDevice(c->device);
     (void)sync_both(c);
     reap(c, true);
-    pool_drop_all(c);
-    for (auto &m : c->masks) { dev_free(c, m.p, m.bytes); sev_put(c, m.clean); }
+    for (auto &m : c->masks) { c->mem.free_uncached(m.p, m.bytes); sev_put(c, m.clean); }
+    c->mem.destroy();
     (void)hipFree(c->g4);
     (void)hipFree(c->g8);
     for (auto &kv : c->g8k) (void)hipFree(kv.second);
-    {   /* (what dev_free left in limbo: its events go) */
-        std::lock_guard<std::mutex> g(c->slab_mu);
-        slab_limbo_poll(c, true);
-    }
-    for (auto &sl : c->slabs) (void)hipFree(sl.base);
-    c->slabs.clear();
     if (c->host_tmp) pin_free(c->host_tmp);
     if (c->slots) (void)hipHostFree(c->slots);
     if (c->dslots) (void)hipFree(c->dslots);
@@ -762,17 +485,7 @@ extern "C" int ntl_ctx_set_pipeline(ntl_ctx *c, int on)
     if (on && !c->wstream_own) return fail(c, NTL_EINVAL, "this context was created without a window stream (NTL_PIPELINE=0)");
     c->pipelined = on != 0;
     c->wstream = on ? c->wstream_own : c->stream;
-    /* Everything queued has run (both streams were drained above), so every cached block is free on either stream: they all
-       move to MAIN's cache.  Switching off, sid() maps every request to MAIN and the window-stage blocks would otherwise lie
-       stranded in pool[SID_W] (counted, never handed out: the next step allocated its temporaries anew); switching on, the
-       window stage's first requests miss its own cache once and are served from then on. */
-    for (auto &kv : c->pool[SID_W]) c->pool[SID_MAIN].insert(kv);
-    c->pool[SID_W].clear();
-    for (auto &kv : c->xpool) {
-        c->pool[SID_MAIN].insert({kv.first, kv.second.p});
-        for (int o = 0; o < NTL_NSID; o++) sev_put(c, kv.second.ev[o]);
-    }
-    c->xpool.clear();
+    c->mem.set_window_stream(c->wstream); /* (both streams were drained above: every cached block moves to MAIN's cache) */
     return NTL_OK;
 }
 
@@ -816,6 +529,7 @@ extern "C" int ntl_prof_reset(ntl_ctx *c)
     if (!c) return NTL_EINVAL;
     prof_collect(c);
     for (auto &kv : c->profs) { kv.second.done_ms = 0; kv.second.launches = 0; }
+    c->mem.driver_allocs = 0; c->mem.driver_ms = 0;
     return NTL_OK;
 }
 
@@ -823,6 +537,11 @@ extern "C" int ntl_prof_get(ntl_ctx *c, const char *name, double *total_ms, uint
 {
     if (!c || !name) return NTL_EINVAL;
     prof_collect(c);
+    if (!strcmp(name, "hipMalloc")) { /* host time of the block cache's misses, counted by the allocator itself */
+        if (total_ms) *total_ms = c->mem.driver_ms;
+        if (launches) *launches = c->mem.driver_allocs;
+        return NTL_OK;
+    }
     auto it = c->profs.find(name);
     if (total_ms) *total_ms = it == c->profs.end() ? 0.0 : it->second.done_ms;
     if (launches) *launches = it == c->profs.end() ? 0 : it->second.launches;
@@ -1291,7 +1010,8 @@ static int sketch_finalize(const ntl_sketch *s);
 
 /* The last reference to an index goes.  Dropped by the context that built it: its device blocks return to that context's cache.
  * Dropped by ANOTHER context (a worker context completing or reaping work that outlived the caller's ntl_index_destroy): the
- * owner's cache and event lists belong to the owner's thread, so the blocks are freed outright (hipFree waits for the device). */
+ * owner's cache and event lists belong to the owner's thread, so the blocks bypass the cache (DevPool::free_uncached, the one call
+ * a foreign thread may make: a slab block waits in limbo for the owner's streams, a single block's hipFree for the device). */
 static void index_unref(const ntl_index *cix, ntl_ctx *by)
 {
     ntl_index *ix = const_cast<ntl_index *>(cix);
@@ -1299,7 +1019,7 @@ static void index_unref(const ntl_index *cix, ntl_ctx *by)
     (void)hipSetDevice(ix->c->device);
     if (by != ix->c) {
         for (DevBuf *b : {&ix->slots, &ix->special, &ix->ctg_len, &ix->cnt, &ix->tags}) {
-            if (b->p) dev_free(ix->c, b->p, b->bytes);
+            ix->c->mem.free_uncached(b->p, b->bytes);
             b->p = nullptr; b->bytes = 0;
         }
         if (ix->built) (void)hipEventDestroy(ix->built);
@@ -1480,13 +1200,12 @@ static int mask_take(ntl_ctx *c, size_t bytes, int sid, CleanMask *out)
         }
     }
     while (c->masks.size() > 4) { /* other batch sizes came and went */
-        dev_free(c, c->masks.front().p, c->masks.front().bytes);
+        c->mem.free_uncached(c->masks.front().p, c->masks.front().bytes);
         sev_put(c, c->masks.front().clean);
         c->masks.pop_front();
     }
     CleanMask m;
-    int rc = dev_alloc(c, want, &m.p);
-    if (rc) return rc;
+    if (c->mem.alloc_uncached(want, &m.p) != DevPool::OK) return fail(c, NTL_ENOMEM, "hipMalloc failed");
     m.bytes = want;
     HIPCHK(c, hipMemsetAsync(m.p, 0, want, c->s(sid)));
     *out = m;
@@ -1736,7 +1455,7 @@ struct SketchWork {
     DevBuf lcnt, lent, loff;
     struct Mask : CleanMask { /* error paths: the mask is not known to be clean any more, it is freed and not kept */
         ntl_ctx *c = nullptr;
-        ~Mask() { if (p) dev_free(c, p, bytes); }
+        ~Mask() { if (p) c->mem.free_uncached(p, bytes); }
     } mask;
     DevBuf strip_lite;
 };

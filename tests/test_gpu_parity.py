@@ -568,6 +568,44 @@ def test_slab_blocks_are_reused_when_the_cache_drops_them(monkeypatch):
         d.close()
 
 
+def test_index_dropped_by_another_context():
+    """An index of context A, used by context B (passed through capi as it is: B's sketch looks its minimizers up in A's table, B's
+    map reads it) and destroyed by the caller while B's calls are only queued: B's completion drops the last reference, and the
+    index's blocks go back to A's allocator from outside A (DevPool::free_uncached: limbo behind A's streams, no cache of A's
+    touched).  B's mappings equal the oracle's; A then serves twenty more contig sketches without another driver allocation."""
+    contigs, reads = pc.fixture_seqs("scaffolds_4.fa"), pc.fixture_seqs("long_reads_4_top5.fa")
+    k, w = 40, 100
+    ctg_len, rlen = np.array([len(s) for s in contigs], np.uint32), np.array([len(s) for s in reads], np.uint32)
+    a, b = capi.Device(0), capi.Device(0)
+    try:
+        with a.batch(contigs) as cb, a.sketch(cb, k, w) as csk:
+            ix = a.index(csk, ctg_len)
+            nix = len(ix)
+            with b.batch(reads) as rb, b.sketch(rb, k, w, index=ix) as rsk, b.map(ix, rsk, rlen, k=k, z=1000) as res:
+                ix.close()  # nothing has been asked for yet: the sketch and the map result hold the index now
+                got = res.download()
+                roff, rh, rp, rs = rsk.download()
+            b.sync()
+            coff, ch, cp, cs = csk.download()
+        ooff, oh, op, os_ = oracle.sketch_batch(b"".join(contigs), pc.offsets_of(contigs), k, w)
+        assert np.array_equal(coff, ooff) and np.array_equal(ch, oh) and np.array_equal(cp, op) and np.array_equal(cs, os_)
+        qoff, qh, qp, qs = oracle.sketch_batch(b"".join(reads), pc.offsets_of(reads), k, w)
+        assert np.array_equal(roff, qoff) and np.array_equal(rh, qh) and np.array_equal(rp, qp) and np.array_equal(rs, qs)
+        oix = oracle.Index(oh, pc.contig_ids(ooff), op, os_)
+        assert nix == len(oix)
+        pc.assert_same_records(got, oracle.map_reads(oix, ctg_len, qoff, rlen, qh, qp, qs, k=k, threads=0, z=1000))
+        assert len(got["maps"]) > 0
+        counts = []
+        for _ in range(20):
+            assert pc.check_sketch(a, contigs, k, w) > 0
+            counts.append(a.prof_get("hipMalloc")[1])
+        assert counts[-1] == counts[0], counts
+        a.sync()
+    finally:
+        b.close()
+        a.close()
+
+
 @pytest.mark.parametrize("name", ["C3", "C5"])
 def test_full_sub_batch_lists_equal_bitmask(name, monkeypatch):
     """A size-independent check at the bench's own sub-batch size (3.9 Gbases of device-generated reads against the full 3-Gbp
