@@ -712,7 +712,7 @@ __global__ __launch_bounds__(MAP_NT) NTL_MAIN_STREAM_SGPRS void map_overflow_ker
    makes the dense copy it hands to the host when it is asked (map_densify_kernel). */
 /* A map result's sums.  The device copy is the result's entry of the context's per-slot array (ntl_hip.hip map_enqueue), zero
    whenever the slot is free: the scans store tot[], the map kernels add to err / n_over, probe_kernel to nfound.  The host's copy
-   is the result's page-locked slot, same layout (the zombie checks read w[1] low = err, w[3] high = nmx). */
+   is the result's page-locked slot, same layout (read through this struct: mapres_finalize and map_check, ntl_hip.hip). */
 struct MapSums { unsigned long long nfound; uint32_t err; uint32_t tot[3]; uint32_t n_over; uint32_t nmx; };
 struct MapSumsOut {
     MapSums *sums;                      /* the device copy: read, and left zero for the next holder of the slot */

@@ -24,6 +24,7 @@
 #include "../../include/ntlink_amd.h"
 #include "dev_common.h"
 #include "dev_pool.h"
+#include "pending.h"
 #include "scan_kernels.h"
 #include "sketch_kernels.h"
 #include "sketch2_kernels.h"
@@ -69,20 +70,6 @@ struct CleanMask {
     hipEvent_t clean = nullptr; /* on MAIN: the clearing kernel has run */
 };
 
-struct PinSlot { uint64_t w[8]; }; /* 64 page-locked bytes a device-side size lands in */
-
-/* what is left of a handle that was destroyed before the device had finished its work: the event, the slot, and what to
-   check in the slot once the event has passed (results nobody looked at still must not have failed silently) */
-struct Zombie {
-    hipEvent_t done = nullptr;
-    PinSlot *slot = nullptr;
-    int kind = 0;      /* 1 sketch (w[0] low = minimizer total vs cap), 2 map result (w[1] low = invariant flag) */
-    uint64_t cap = 0;
-    std::shared_ptr<std::atomic<float>> hitf; /* 2: where the batch's hit fraction goes (MapSums: nfound / nmx) */
-    const struct ntl_index *ix = nullptr; /* the index the queued kernels read: its reference is dropped when they have run */
-    const struct ntl_batch *batch = nullptr; /* 2: the batch whose lengths the map kernels read (d_seq_len): likewise */
-};
-
 struct ntl_ctx {
     int device = 0;
     hipStream_t stream = nullptr;  /* MAIN */
@@ -90,14 +77,12 @@ struct ntl_ctx {
     hipStream_t wstream_own = nullptr; /* the second stream itself (ntl_ctx_set_pipeline switches wstream between it and MAIN) */
     bool pipelined = false;
     std::string err;
-    std::string async_err;         /* first failure of work whose handle was already gone: reported by ntl_ctx_sync */
     std::string devname;
     int n_cu = 1;                  /* compute units of the device: the grid of a kernel whose wavefronts stay resident */
     std::map<const void *, int> occ; /* kernel -> workgroups one CU holds (hipOccupancyMaxActiveBlocksPerMultiprocessor, asked once) */
     bool prof = false;
     std::map<std::string, ProfEntry> profs;
     std::vector<hipEvent_t> ev_free;    /* timing events (profiling spans) */
-    std::vector<hipEvent_t> sev_free;   /* ordering events (no timing) */
     void *g4 = nullptr;                 /* device copy of the four-base init table */
     void *g8 = nullptr;                 /* device copy of the eight-base init table (1 MB) */
     std::map<int, void *> g8k;          /* k -> the two k-dependent ring forms of g8 the fast window pass reads (1 MB per k, sketch2_kernels.h) */
@@ -105,11 +90,9 @@ struct ntl_ctx {
     std::deque<CleanMask> masks;
     void *host_tmp = nullptr;           /* page-locked bounce buffer for record downloads (grows, never shrinks) */
     size_t host_tmp_cap = 0;
-    PinSlot *slots = nullptr;
-    PinSlot *slots_dev = nullptr;       /* the same slots as the kernels address them (mapped: the kernels write sizes and sums there) */
-    PinSlot *dslots = nullptr;          /* device memory, one entry per slot: a map result's sums (MapSums), zero while the slot is free */
-    std::vector<uint32_t> slot_free;
-    std::deque<Zombie> zombies;
+    PinSlot *slots = nullptr;           /* the page-locked slots, and ... */
+    PinSlot *dslots = nullptr;          /* ... device memory, one entry per slot: a map result's sums (MapSums), zero while the slot is free */
+    PendingQueue pq;                    /* the slots, the ordering events and the handles destroyed before their work had run (pending.h) */
     hipEvent_t throttle[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint64_t n_enqueued = 0;            /* sketches queued so far: the host runs at most 8 of them ahead of the device */
     hipStream_t s(int sid) const { return sid == SID_W ? wstream : stream; }
@@ -201,94 +184,16 @@ static int fail(ntl_ctx *c, int code, const std::string &msg)
             return fail(ctx, NTL_EDEVICE, std::string(#expr) + ": " + hipGetErrorString(e_));     \
     } while (0)
 
-/* ordering events come from a free list (creating one costs tens of microseconds) */
-static hipEvent_t sev_get(ntl_ctx *c)
-{
-    hipEvent_t e = nullptr;
-    if (!c->sev_free.empty()) { e = c->sev_free.back(); c->sev_free.pop_back(); return e; }
-    /* hipEventBlockingSync: a host thread that waits on such an event sleeps until the interrupt instead of spinning -- the pair
-       driver's worker threads wait for uploads and results most of the time, and on a host that grants the process 16 cores
-       (the GPU boxes: 256 visible, cpu.max = 16) every spinning thread is a parser thread less */
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming | hipEventBlockingSync) != hipSuccess) return nullptr;
-    return e;
-}
-static void sev_put(ntl_ctx *c, hipEvent_t e) { if (e) c->sev_free.push_back(e); }
-
-/* Wait for an event the host needs NOW (a lazily completed handle): polls for a while before it blocks -- a blocking wait
- * is woken by an interrupt some tens of microseconds after the event has passed. */
-static hipError_t wait_hot(hipEvent_t e)
-{
-    static const int spin_us = [] { const char *v = getenv("NTL_SYNC_SPIN_US"); return v ? atoi(v) : 100; }();
-    if (spin_us > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        for (;;) {
-            const hipError_t q = hipEventQuery(e);
-            if (q == hipSuccess) return hipSuccess;
-            if (q != hipErrorNotReady) return q;
-            if (std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count() > spin_us) break;
-        }
-    }
-    return hipEventSynchronize(e);
-}
-
 /* waits until everything queued on MAIN so far has finished -- on an event, so that the thread sleeps (hipStreamSynchronize
    spins for a while first) */
 static hipError_t main_wait(ntl_ctx *c)
 {
-    hipEvent_t e = sev_get(c);
+    hipEvent_t e = c->pq.event_get();
     if (!e) return hipStreamSynchronize(c->stream);
     hipError_t rc = hipEventRecord(e, c->stream);
     if (rc == hipSuccess) rc = hipEventSynchronize(e);
-    sev_put(c, e);
+    c->pq.event_put(e);
     return rc;
-}
-
-static PinSlot *slot_get(ntl_ctx *c);
-static void index_unref(const struct ntl_index *ix, ntl_ctx *by);
-static void batch_unref(const struct ntl_batch *b);
-/* a slot as the kernels address it, and its entry of the device-side array */
-static PinSlot *slot_dev(const ntl_ctx *c, const PinSlot *p) { return c->slots_dev + (p - c->slots); }
-static PinSlot *slot_dsums(const ntl_ctx *c, const PinSlot *p) { return c->dslots + (p - c->slots); }
-static void slot_put(ntl_ctx *c, PinSlot *p) { if (p) c->slot_free.push_back((uint32_t)(p - c->slots)); }
-
-/* zombies whose work has finished: check what they carried, recycle event and slot.  block: wait for the oldest one. */
-static void reap(ntl_ctx *c, bool block)
-{
-    while (!c->zombies.empty()) {
-        Zombie &z = c->zombies.front();
-        hipError_t q = hipEventQuery(z.done);
-        if (q == hipErrorNotReady) {
-            if (!block) return;
-            q = hipEventSynchronize(z.done);
-            block = false;
-        }
-        if (q != hipSuccess && c->async_err.empty()) c->async_err = std::string("device work failed: ") + hipGetErrorString(q);
-        if (q == hipSuccess && z.slot && c->async_err.empty()) {
-            if (z.kind == 1 && ((uint32_t)z.slot->w[0] > z.cap || (uint32_t)(z.slot->w[1] >> 32)))
-                c->async_err = "a sketch held more minimizers than its record array and was destroyed before anybody asked for its count";
-            if (z.kind == 2 && (uint32_t)z.slot->w[1])
-                c->async_err = "an accepted contig appeared twice in one read (bin/ntlink_utils.py:262-266)";
-            if (z.kind == 2 && z.hitf) { /* MapSums: w[0] = nfound, high half of w[3] = nmx */
-                const uint32_t nmx = (uint32_t)(z.slot->w[3] >> 32);
-                if (nmx) z.hitf->store((float)((double)z.slot->w[0] / (double)nmx), std::memory_order_relaxed);
-            }
-        }
-        sev_put(c, z.done);
-        slot_put(c, z.slot);
-        index_unref(z.ix, c);
-        batch_unref(z.batch);
-        c->zombies.pop_front();
-    }
-}
-
-static PinSlot *slot_get(ntl_ctx *c)
-{
-    if (c->slot_free.empty()) reap(c, true);
-    if (c->slot_free.empty()) return nullptr;
-    PinSlot *p = c->slots + c->slot_free.back();
-    c->slot_free.pop_back();
-    memset(p, 0, sizeof *p);
-    return p;
 }
 
 /* A device buffer that returns to the context's block cache (dev_pool.h): the RAII handle over take / give.  touch() notes a second
@@ -395,15 +300,16 @@ extern "C" int ntl_ctx_create(int device, ntl_ctx **out)
         /* Kernels write the sizes and sums that come back to the host straight into the slots (ntl_host_store32/64): the slots are
            mapped into the device's address space and coherent (fine-grained: a device store goes to host memory, not into the
            device's L2), whatever HIP_HOST_COHERENT says -- hipHostMallocDefault leaves coherence to that variable. */
+        PinSlot *slots_dev = nullptr; /* the same slots as the kernels address them */
 #ifdef NTL_SIM
         if (hipHostMalloc((void **)&c->slots, NTL_NSLOTS * sizeof(PinSlot), hipHostMallocDefault) != hipSuccess) {
             delete c;
             return NTL_EDEVICE;
         }
-        c->slots_dev = c->slots;
+        slots_dev = c->slots;
 #else
         if (hipHostMalloc((void **)&c->slots, NTL_NSLOTS * sizeof(PinSlot), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess ||
-            hipHostGetDevicePointer((void **)&c->slots_dev, c->slots, 0) != hipSuccess) {
+            hipHostGetDevicePointer((void **)&slots_dev, c->slots, 0) != hipSuccess) {
             delete c;
             return NTL_EDEVICE;
         }
@@ -415,7 +321,7 @@ extern "C" int ntl_ctx_create(int device, ntl_ctx **out)
         }
         uint32_t nslots = NTL_NSLOTS; /* NTL_NSLOTS (tests): fewer, so that a handful of handles reaches the bound */
         if (const char *e = getenv("NTL_NSLOTS")) nslots = (uint32_t)std::min<long>(NTL_NSLOTS, std::max<long>(2, atol(e)));
-        for (uint32_t i = 0; i < nslots; i++) c->slot_free.push_back(nslots - 1 - i);
+        c->pq.setup(c->slots, slots_dev, c->dslots, nslots, c);
     }
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess) {
@@ -451,8 +357,8 @@ extern "C" void ntl_ctx_destroy(ntl_ctx *c)
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)sync_both(c);
-    reap(c, true);
-    for (auto &m : c->masks) { c->mem.free_uncached(m.p, m.bytes); sev_put(c, m.clean); }
+    c->pq.reap(true);
+    for (auto &m : c->masks) { c->mem.free_uncached(m.p, m.bytes); c->pq.event_put(m.clean); }
     c->mem.destroy();
     (void)hipFree(c->g4);
     (void)hipFree(c->g8);
@@ -463,8 +369,8 @@ extern "C" void ntl_ctx_destroy(ntl_ctx *c)
     for (auto &kv : c->profs)
         for (auto &sp : kv.second.spans) { (void)hipEventDestroy(sp.first); (void)hipEventDestroy(sp.second); }
     for (auto e : c->ev_free) (void)hipEventDestroy(e);
-    for (auto &e : c->throttle) sev_put(c, e);
-    for (auto e : c->sev_free) (void)hipEventDestroy(e);
+    for (auto &e : c->throttle) c->pq.event_put(e);
+    c->pq.destroy();
     if (c->wstream_own) (void)hipStreamDestroy(c->wstream_own);
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -481,7 +387,7 @@ extern "C" int ntl_ctx_set_pipeline(ntl_ctx *c, int on)
     if (!c) return NTL_EINVAL;
     (void)hipSetDevice(c->device);
     HIPCHK(c, sync_both(c));
-    reap(c, true);
+    c->pq.reap(true);
     if (on && !c->wstream_own) return fail(c, NTL_EINVAL, "this context was created without a window stream (NTL_PIPELINE=0)");
     c->pipelined = on != 0;
     c->wstream = on ? c->wstream_own : c->stream;
@@ -494,10 +400,10 @@ extern "C" int ntl_ctx_sync(ntl_ctx *c)
     if (!c) return NTL_EINVAL;
     (void)hipSetDevice(c->device);
     HIPCHK(c, sync_both(c));
-    reap(c, true);
-    if (!c->async_err.empty()) {
-        const std::string m = c->async_err;
-        c->async_err.clear();
+    c->pq.reap(true);
+    if (!c->pq.async_err.empty()) {
+        const std::string m = c->pq.async_err;
+        c->pq.async_err.clear();
         return fail(c, NTL_EINTERNAL, m);
     }
     return NTL_OK;
@@ -602,7 +508,7 @@ static void batch_unref(const ntl_batch *cb)
     ntl_batch *b = const_cast<ntl_batch *>(cb);
     if (b && --b->refs == 0) {
         (void)hipSetDevice(b->c->device);
-        sev_put(b->c, b->ready);
+        b->c->pq.event_put(b->ready);
         delete b;
     }
 }
@@ -870,7 +776,7 @@ extern "C" int ntl_synth_genome(ntl_ctx *c, uint64_t seed, const uint32_t *len, 
     const uint64_t nw = b->nwords_packed;
     hipLaunchKernelGGL(synth_genome_kernel, dim3((unsigned)((nw / 2 + 256) / 256)), dim3(256), 0, c->stream, b->packed.as<uint32_t>(), nw, seed);
     HIPCHK(c, hipGetLastError());
-    if (c->pipelined && (b->ready = sev_get(c))) HIPCHK(c, hipEventRecord(b->ready, c->stream));
+    if (c->pipelined && (b->ready = c->pq.event_get())) HIPCHK(c, hipEventRecord(b->ready, c->stream));
     *out = b.release();
     return NTL_OK;
 }
@@ -995,14 +901,9 @@ struct ntl_sketch {
     /* the lookup's hit count has not reached the slot yet: the next kernel queued behind the lookup on MAIN copies it there -- the
        gather of the first map result on this sketch (map_enqueue), or sketch_nfound_kernel when the count is asked for first */
     mutable bool nfound_owed = false;
-    /* lazy completion */
-    mutable bool pending = false;
-    mutable hipEvent_t done = nullptr;
-    mutable PinSlot *slot = nullptr;
+    mutable Pending lz;                   /* lazy completion (pending.h); holds[0]: the index the sketch was made for */
     mutable uint64_t gen = 0;             /* bumped when the sketch had to be made again with larger arrays */
-    mutable int failed = 0;               /* sticky error code of the completion */
     const ntl_batch *src = nullptr;       /* held (refs) while pending: a sketch that overflowed is redone from it */
-    const ntl_index *src_ix = nullptr;
     int k = 0, w = 0;
 };
 
@@ -1023,25 +924,40 @@ static void index_unref(const ntl_index *cix, ntl_ctx *by)
             b->p = nullptr; b->bytes = 0;
         }
         if (ix->built) (void)hipEventDestroy(ix->built);
-    } else sev_put(ix->c, ix->built);
+    } else ix->c->pq.event_put(ix->built);
     delete ix;
+}
+
+/* what a Pending holds for its queued kernels (pending.h) */
+static void hold_index(const void *ix, void *by) { index_unref((const ntl_index *)ix, (ntl_ctx *)by); }
+static void hold_batch(const void *b, void *) { batch_unref((const ntl_batch *)b); }
+
+/* the check of a sketch that was destroyed before anybody asked for its count; arg: the records its arrays hold */
+static const char *sketch_check(const PinSlot &slot, uint64_t cap, std::atomic<float> *)
+{
+    const SketchSums &hs = (const SketchSums &)slot;
+    return hs.total_mx > cap || hs.list_fail ? "a sketch held more minimizers than its record array and was destroyed before anybody asked for its count" : nullptr;
+}
+
+/* An error path: whatever was queued must not outlive what the handle lets go, so the device is drained first; a map result's device
+   sums (dsums) are in an unknown state then and are zeroed again for the slot's next holder. */
+static int pending_abort(ntl_ctx *c, Pending &p, int rc, bool map_scrub = false)
+{
+    (void)sync_both(c);
+    if (map_scrub && p.slot) (void)hipMemset(c->pq.slot_dsums(p.slot), 0, sizeof(PinSlot));
+    p.pending = false;
+    p.failed = rc;
+    p.settle(c->pq);
+    return rc;
 }
 
 static void sketch_unref(const ntl_sketch *cs)
 {
     ntl_sketch *s = const_cast<ntl_sketch *>(cs);
     if (!s || --s->refs != 0) return;
-    ntl_ctx *c = s->c;
-    (void)hipSetDevice(c->device);
-    if (s->pending) { /* nobody asked: the device blocks go back now (stream-ordered), event and slot when the work is done */
-        Zombie z;
-        z.done = s->done; z.slot = s->slot; z.kind = 1; z.cap = s->cap; z.ix = s->src_ix;
-        c->zombies.push_back(z);
-    } else {
-        sev_put(c, s->done);
-        slot_put(c, s->slot);
-        index_unref(s->src_ix, c);
-    }
+    (void)hipSetDevice(s->c->device);
+    /* nobody asked: the device blocks go back now (stream-ordered), event, slot and index when the work is done */
+    s->lz.orphan(s->c->pq, sketch_check, s->cap);
     if (s->src) batch_unref(s->src);
     delete s;
 }
@@ -1192,7 +1108,7 @@ static int mask_take(ntl_ctx *c, size_t bytes, int sid, CleanMask *out)
             if (m.bytes >= want && m.bytes <= want + want / 4 + (1 << 20)) {
                 c->masks.erase(c->masks.begin() + (long)i);
                 if (m.clean && c->s(sid) != c->stream) (void)hipStreamWaitEvent(c->s(sid), m.clean, 0);
-                sev_put(c, m.clean);
+                c->pq.event_put(m.clean);
                 m.clean = nullptr;
                 *out = m;
                 return NTL_OK;
@@ -1201,7 +1117,7 @@ static int mask_take(ntl_ctx *c, size_t bytes, int sid, CleanMask *out)
     }
     while (c->masks.size() > 4) { /* other batch sizes came and went */
         c->mem.free_uncached(c->masks.front().p, c->masks.front().bytes);
-        sev_put(c, c->masks.front().clean);
+        c->pq.event_put(c->masks.front().clean);
         c->masks.pop_front();
     }
     CleanMask m;
@@ -1580,9 +1496,9 @@ static int sketch_window_stage(ntl_ctx *c, const ntl_batch *b, int k, const Wind
     ProfSpan sp(c, "sketch_redo", wsid);
     SketchArgs R = A;
     R.redo_count = B.redo_count; R.redo_list = B.redo_list;
-    /* the redo pass writes the two counts into the slot (`redo` never leaves the window stream); s->done, on MAIN behind the
+    /* the redo pass writes the two counts into the slot (`redo` never leaves the window stream); s->lz.done, on MAIN behind the
        emit kernel, is behind it too (window stage -> emit) */
-    R.redo_out = &((SketchSums *)slot_dev(c, s->slot))->redo_n;
+    R.redo_out = &((SketchSums *)c->pq.slot_dev(s->lz.slot))->redo_n;
     launch_mask<16>(c, R, (unsigned)ub_strips, true, false, nt);
     if (b->any_multi) launch_mask<16>(c, A, (unsigned)ub_strips, false, true, nt);
     HIPCHK(c, hipGetLastError());
@@ -1651,7 +1567,7 @@ static int sketch_emit_stage(ntl_ctx *c, const ntl_batch *b, int k, const Window
            kernels leave such a sketch alone and sketch_finalize makes it again through the bitmask) */
         W.strip_first.touch(SID_MAIN); W.strip_tab.touch(SID_MAIN);
         if ((rc = device_scan(c, Ls.cnt, W.loff.as<uint32_t>(), ub_strips, nullptr, 1, &dsums->total_mx))) return rc;
-        SketchSums *hd = (SketchSums *)slot_dev(c, s->slot); /* the true total and whether the lists ran out, for the host */
+        SketchSums *hd = (SketchSums *)c->pq.slot_dev(s->lz.slot); /* the true total and whether the lists ran out, for the host */
         hipLaunchKernelGGL(list_fail_kernel, dim3(1), dim3(64), 0, ms, (const uint32_t *)Ls.ctl, &dsums->total_mx, &dsums->list_fail, tile_next.as<uint32_t>(),
                            &hd->total_mx, &hd->list_fail);
         hipLaunchKernelGGL(mx_off_from_strips_kernel, dim3((unsigned)((nseq + 256) / 256)), dim3(256), 0, ms, (const uint32_t *)W.strip_first.as<uint32_t>(),
@@ -1694,7 +1610,7 @@ static int sketch_emit_stage(ntl_ctx *c, const ntl_batch *b, int k, const Window
     /* the emit kernel is the last reader of the bitmask and clears the words it read: the mask goes back clean */
     if (W.mask.p) {
         CleanMask m = W.mask;
-        m.clean = sev_get(c);
+        m.clean = c->pq.event_get();
         if (m.clean) HIPCHK(c, hipEventRecord(m.clean, ms));
         else HIPCHK(c, hipStreamSynchronize(ms));
         c->masks.push_back(m);
@@ -1703,7 +1619,7 @@ static int sketch_emit_stage(ntl_ctx *c, const ntl_batch *b, int k, const Window
     /* (the map kernels read the lengths of the sketched sequences from the batch itself: ntl_map_run holds it) */
     s->nfound_owed = false;
     if (!lists) { /* the bitmask path (off the hot path): the totals come back by copies */
-        SketchSums *hs = (SketchSums *)s->slot;
+        SketchSums *hs = (SketchSums *)s->lz.slot;
         HIPCHK(c, hipMemcpyAsync(&hs->total_mx, &dsums->total_mx, 4, hipMemcpyDeviceToHost, ms));
         if (ix) HIPCHK(c, hipMemcpyAsync(&hs->nfound, &dsums->nfound, 8, hipMemcpyDeviceToHost, ms));
     } else s->nfound_owed = ix != nullptr; /* (list_fail_kernel wrote the total and the flag) */
@@ -1711,7 +1627,7 @@ static int sketch_emit_stage(ntl_ctx *c, const ntl_batch *b, int k, const Window
 }
 
 /* Queues one sketch: the window stage on the window stream, count + emit (+ index lookup) on MAIN behind it.  Nothing
- * waits; the minimizer total lands in the sketch's page-locked slot and s->done is recorded behind it.  `cap` = records the
+ * waits; the minimizer total lands in the sketch's page-locked slot and s->lz.done is recorded behind it.  `cap` = records the
  * arrays hold: a guess from the expected density (sketch_finalize makes the sketch again if the batch was denser), or the
  * exact total on that second round. */
 static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const ntl_index *ix, ntl_sketch *s, uint64_t cap)
@@ -1719,7 +1635,7 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     /* the host runs at most 8 sketches ahead of the device */
     hipEvent_t &throttle = c->throttle[c->n_enqueued & 7u];
     if (throttle) (void)hipEventSynchronize(throttle);
-    reap(c, false);
+    c->pq.reap(false);
     WindowPlan P;
     int rc;
     if ((rc = window_plan(c, b, k, w, s->no_lists, P))) return rc;
@@ -1728,15 +1644,15 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     if ((rc = sketch_prepare(c, b, k, w, P, s, W))) return rc;
     if ((rc = sketch_window_stage(c, b, k, P, s, W))) return rc;
     if (W.ws != W.ms) { /* window stage -> emit */
-        hipEvent_t e = sev_get(c);
+        hipEvent_t e = c->pq.event_get();
         if (!e) return fail(c, NTL_EDEVICE, "hipEventCreate failed");
         HIPCHK(c, hipEventRecord(e, W.ws));
         HIPCHK(c, hipStreamWaitEvent(W.ms, e, 0));
-        sev_put(c, e); /* the wait holds what it needs; the handle may be recorded again */
+        c->pq.event_put(e); /* the wait holds what it needs; the handle may be recorded again */
     }
     if ((rc = sketch_emit_stage(c, b, k, P, ix, s, cap, W))) return rc;
-    HIPCHK(c, hipEventRecord(s->done, W.ms));
-    if (!throttle) throttle = sev_get(c);
+    HIPCHK(c, hipEventRecord(s->lz.done, W.ms));
+    if (!throttle) throttle = c->pq.event_get();
     if (throttle) HIPCHK(c, hipEventRecord(throttle, W.ms));
     c->n_enqueued++;
     s->strips = P.strips; s->from_lists = P.lists;
@@ -1745,7 +1661,7 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     I.pass = (int32_t)P.pass; I.nt = P.nt; I.C = P.C; I.NWO = P.G.NWO;
     I.big = P.big; I.direct = P.direct; I.lists = P.lists; I.thresh = P.thresh;
     if (P.pass == WP_WAVE) wave_shape_numbers(P.shape, &I.wave_wavefronts);
-    s->pending = true;
+    s->lz.pending = true;
     return NTL_OK; /* (W's temporaries return to the context's cache here) */
 }
 
@@ -1758,12 +1674,10 @@ static int sketch_run_impl(ntl_ctx *c, const ntl_batch *b, int k, int w, const n
     int C, nt, rc; bool small;
     if ((rc = sketch_geometry(c, k, w, G, C, nt, small))) return rc; /* (a window this build cannot sketch: refused before anything is made) */
     ntl_sketch *s = new ntl_sketch();
-    s->c = c; s->nseq = b->nseq; s->k = k; s->w = w; s->src_ix = ix;
+    s->c = c; s->nseq = b->nseq; s->k = k; s->w = w;
     s->no_records = no_records && ix;
-    if (ix) ix->refs++;
-    s->done = sev_get(c);
-    s->slot = slot_get(c);
-    if (!s->done || !s->slot) { sketch_unref(s); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
+    if (ix) { ix->refs++; s->lz.holds[0] = {ix, hold_index}; }
+    if (!s->lz.arm(c->pq)) { sketch_unref(s); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
     /* The record array is sized from the expected density before the count is known (the device goes straight on to the
        emit kernel); a batch denser than the guess (low-complexity sequence) is sketched a second time into exact-size
        arrays when its count is asked for (sketch_finalize). */
@@ -1774,8 +1688,7 @@ static int sketch_run_impl(ntl_ctx *c, const ntl_batch *b, int k, int w, const n
     const_cast<ntl_batch *>(b)->refs++;
     s->src = b;
     if ((rc = sketch_enqueue(c, b, k, w, ix, s, cap_guess))) {
-        (void)sync_both(c); /* whatever was queued must not outlive the buffers the error path lets go */
-        s->pending = false;
+        pending_abort(c, s->lz, rc);
         sketch_unref(s);
         return rc;
     }
@@ -1788,38 +1701,37 @@ static int sketch_run_impl(ntl_ctx *c, const ntl_batch *b, int k, int w, const n
 static int sketch_finalize(const ntl_sketch *cs)
 {
     ntl_sketch *s = const_cast<ntl_sketch *>(cs);
-    if (!s->pending) return s->failed;
+    Pending &lz = s->lz;
+    if (!lz.pending) return lz.failed;
     ntl_ctx *c = s->c;
     (void)hipSetDevice(c->device);
     for (int round = 0;; round++) {
         if (s->nfound_owed) { /* no map kernel took the hit count: a kernel of its own, behind the lookup, and the event behind that */
             s->nfound_owed = false;
             hipLaunchKernelGGL(sketch_nfound_kernel, dim3(1), dim3(64), 0, c->stream, (const unsigned long long *)&s->sums.as<SketchSums>()->nfound,
-                               &((SketchSums *)slot_dev(c, s->slot))->nfound);
+                               &((SketchSums *)c->pq.slot_dev(lz.slot))->nfound);
             hipError_t le = hipGetLastError();
-            if (le == hipSuccess) le = hipEventRecord(s->done, c->stream);
-            if (le != hipSuccess) { (void)sync_both(c); s->pending = false; s->failed = fail(c, NTL_EDEVICE, std::string("sketch: ") + hipGetErrorString(le)); break; }
+            if (le == hipSuccess) le = hipEventRecord(lz.done, c->stream);
+            if (le != hipSuccess) { pending_abort(c, lz, fail(c, NTL_EDEVICE, std::string("sketch: ") + hipGetErrorString(le))); break; }
         }
-        const hipError_t e = wait_hot(s->done);
-        s->pending = false;
-        if (e != hipSuccess) { s->failed = fail(c, NTL_EDEVICE, std::string("sketch: ") + hipGetErrorString(e)); break; }
-        const SketchSums hs = *(const SketchSums *)s->slot;
+        const hipError_t e = lz.wait();
+        lz.pending = false;
+        if (e != hipSuccess) { lz.failed = fail(c, NTL_EDEVICE, std::string("sketch: ") + hipGetErrorString(e)); break; }
+        const SketchSums hs = *(const SketchSums *)lz.slot;
         s->count = hs.total_mx; s->redo_strips = hs.redo_n; s->fallback_strips = hs.fb_n; s->nfound = hs.nfound;
         if (s->count <= s->cap && !hs.list_fail) break;
-        if (round || !s->src) { s->failed = fail(c, NTL_EINTERNAL, "sketch: the exact-size round overflowed again"); break; }
+        if (round || !s->src) { lz.failed = fail(c, NTL_EINTERNAL, "sketch: the exact-size round overflowed again"); break; }
         if (hs.list_fail) s->no_lists = true; /* the strips' lists ran out of pool (the counts are right): once more, through the bitmask */
         s->gen++;
-        memset(s->slot, 0, sizeof(PinSlot));
-        const int rc = sketch_enqueue(c, s->src, s->k, s->w, s->src_ix, s, s->count);
-        if (rc) { (void)sync_both(c); s->pending = false; s->failed = rc; break; }
+        memset(lz.slot, 0, sizeof(PinSlot));
+        const int rc = sketch_enqueue(c, s->src, s->k, s->w, (const ntl_index *)lz.holds[0].p, s, s->count);
+        if (rc) { pending_abort(c, lz, rc); break; }
     }
     if (s->src) { batch_unref(s->src); s->src = nullptr; }
     /* complete: what only a pending sketch needs goes back now, not when the handle is destroyed -- a context has NTL_NSLOTS
        page-locked slots, and callers keep thousands of completed sketches alive */
-    index_unref(s->src_ix, c); s->src_ix = nullptr;
-    sev_put(c, s->done); s->done = nullptr;
-    slot_put(c, s->slot); s->slot = nullptr;
-    return s->failed;
+    lz.settle(c->pq);
+    return lz.failed;
 }
 
 extern "C" int ntl_sketch_run(ntl_ctx *c, const ntl_batch *b, int k, int w, ntl_sketch **out)
@@ -2074,7 +1986,7 @@ extern "C" int ntl_index_build(ntl_ctx *c, const ntl_sketch *ctg, const uint32_t
         HIPCHK(c, hipMemcpyAsync(ix->tags.as<uint8_t>() + ix->nslots, ix->tags.p, 8, hipMemcpyDeviceToDevice, c->stream));
     }
     (void)size;
-    if ((ix->built = sev_get(c))) HIPCHK(c, hipEventRecord(ix->built, c->stream));
+    if ((ix->built = c->pq.event_get())) HIPCHK(c, hipEventRecord(ix->built, c->stream));
     *out = ix_guard.release();
     return NTL_OK;
 }
@@ -2110,19 +2022,13 @@ struct ntl_mapres {
     mutable DevBuf hits;             /* per-read regions (read r's hits from mx_off[r] on); maps[].hit_off points into them */
     mutable DevBuf maps_dense, hits_dense, hit_doff; /* made on demand: the dense copy ntl_mapres_download hands out; u32[n_maps + 1] dense offsets */
     mutable bool dense_made = false, doff_made = false;
-    /* lazy completion */
-    mutable bool pending = false;
-    mutable hipEvent_t done = nullptr;
-    mutable PinSlot *slot = nullptr;
-    mutable int failed = 0;
-    const ntl_index *ix = nullptr;
+    mutable Pending lz;                 /* lazy completion (pending.h); holds[0]: the index, holds[1]: the batch whose lengths the kernels read */
     const ntl_sketch *reads = nullptr;  /* held (refs) while pending */
     uint64_t reads_gen = 0;             /* generation of the sketch the kernels were queued on */
     ntl_map_params params;
     std::shared_ptr<std::atomic<float>> hitf; /* the index's hit fraction (the index itself may be gone when this completes) */
     DevBuf rlen_own;                    /* read lengths uploaded by this call (sketches that did not come from a batch) */
-    const uint32_t *d_rlen = nullptr;   /* the read lengths the kernels read: rlen_own, or the batch's own (d_seq_len) */
-    const ntl_batch *batch = nullptr;   /* ... whose batch is held (refs) until the kernels have run */
+    const uint32_t *d_rlen = nullptr;   /* the read lengths the kernels read: rlen_own, or the batch's own (d_seq_len; lz holds the batch) */
 };
 
 /* Queues the lookup (when the sketch does not carry candidates), the map kernels, the offset scans and the gather on MAIN.
@@ -2135,7 +2041,7 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
     if (!have_cand) { /* the lookup pass runs over the records: their number sizes its grid */
         if (int frc = sketch_finalize(reads)) return frc;
     }
-    const uint64_t nmx = reads->pending ? reads->cap : reads->count;
+    const uint64_t nmx = reads->lz.pending ? reads->cap : reads->count;
     const ntl_map_params *params = &R->params;
     int rc;
     hipStream_t ms = c->stream;
@@ -2150,10 +2056,10 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
         (rc = R->maps.alloc(c, cap * sizeof(MapRec))) || (rc = R->hits.alloc(c, cap * sizeof(HitRec))) ||
         (rc = R->pafs.alloc(c, cap * sizeof(PafRec)))) return rc;
     /* The sums: the result's entry of the per-slot device array.  It is zero whenever the slot is free -- map_gather_kernel, the last
-       kernel of this work, hands the sums to the slot and leaves the entry zero; the slot is recycled only after R->done, behind it
-       (or, on the error paths, after map_scrub) -- and every kernel that adds to it runs on MAIN behind the gather of the slot's
+       kernel of this work, hands the sums to the slot and leaves the entry zero; the slot is recycled only after R->lz.done, behind it
+       (or, on the error paths, after pending_abort zeroed it) -- and every kernel that adds to it runs on MAIN behind the gather of the slot's
        previous holder.  The lookup's count of a sketch made for this index stays where the lookup left it (SketchSums::nfound). */
-    MapSums *dsums = (MapSums *)slot_dsums(c, R->slot);
+    MapSums *dsums = (MapSums *)c->pq.slot_dsums(R->lz.slot);
     if (ix->c != c && ix->built) HIPCHK(c, hipStreamWaitEvent(ms, ix->built, 0));
     if (!have_cand) {
         ProfSpan sp(c, "probe");
@@ -2185,7 +2091,7 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
     A.scr = scr.as<uint32_t>(); A.scr_stride = cap; A.err = &dsums->err;
     A.over_list = over.as<uint32_t>(); A.over_count = &dsums->n_over;
     /* a sketch whose count is not known yet may have overflowed its arrays: the kernels look at its total and leave it alone */
-    A.mx_total = reads->pending ? &reads->sums.as<SketchSums>()->total_mx : nullptr;
+    A.mx_total = reads->lz.pending ? &reads->sums.as<SketchSums>()->total_mx : nullptr;
     A.mx_cap = (uint32_t)std::min<uint64_t>(reads->cap, 0xFFFFFFFFull);
     if (nreads) {
         {
@@ -2211,46 +2117,39 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
         MapSumsOut O;
         O.sums = dsums;
         O.nfound = have_cand ? &reads->sums.as<SketchSums>()->nfound : &dsums->nfound;
-        O.slot = (unsigned long long *)slot_dev(c, R->slot);
+        O.slot = (unsigned long long *)c->pq.slot_dev(R->lz.slot);
         /* the sketch's own hit count, if nothing has copied it yet: its event moves behind this kernel (sketch_finalize waits for it) */
         O.sk_nfound = nullptr;
-        if (have_cand && reads->pending && reads->nfound_owed) O.sk_nfound = &((SketchSums *)slot_dev(c, reads->slot))->nfound;
+        if (have_cand && reads->lz.pending && reads->nfound_owed) O.sk_nfound = &((SketchSums *)c->pq.slot_dev(reads->lz.slot))->nfound;
         hipLaunchKernelGGL(map_gather_kernel, dim3((unsigned)nreads), dim3(64), 0, ms, A, (const uint32_t *)o,
                            (const uint32_t *)(o + 2 * (nreads + 1)), R->maps.as<MapRec>(), R->pafs.as<PafRec>(), O);
         HIPCHK(c, hipGetLastError());
         if (O.sk_nfound) {
-            HIPCHK(c, hipEventRecord(reads->done, ms));
+            HIPCHK(c, hipEventRecord(reads->lz.done, ms));
             reads->nfound_owed = false;
         }
     }
     /* (no reads: no kernel, and the slot keeps the zeros slot_get left in it) */
-    HIPCHK(c, hipEventRecord(R->done, ms));
-    R->pending = true;
+    HIPCHK(c, hipEventRecord(R->lz.done, ms));
+    R->lz.pending = true;
     R->reads_gen = reads->gen;
     return NTL_OK;
 }
 
-/* an error path left the result's device sums in an unknown state (the device is idle: sync_both): zero again for the slot's next holder */
-static void map_scrub(ntl_ctx *c, const ntl_mapres *R)
+/* The check of a map result, completed or destroyed before anybody asked: the invariant flag, and the batch's hit fraction for the
+   index's next batch */
+static const char *map_check(const PinSlot &slot, uint64_t, std::atomic<float> *hitf)
 {
-    if (R->slot) (void)hipMemset(slot_dsums(c, R->slot), 0, sizeof(PinSlot));
+    const MapSums &hs = (const MapSums &)slot;
+    if (hitf && hs.nmx) hitf->store((float)((double)hs.nfound / (double)hs.nmx), std::memory_order_relaxed);
+    return hs.err ? "an accepted contig appeared twice in one read (bin/ntlink_utils.py:262-266)" : nullptr;
 }
 
 static void mapres_free(ntl_mapres *R)
 {
     if (!R) return;
-    ntl_ctx *c = R->c;
-    (void)hipSetDevice(c->device);
-    if (R->pending) {
-        Zombie z;
-        z.done = R->done; z.slot = R->slot; z.kind = 2; z.hitf = R->hitf; z.ix = R->ix; z.batch = R->batch;
-        c->zombies.push_back(z);
-    } else {
-        sev_put(c, R->done);
-        slot_put(c, R->slot);
-        index_unref(R->ix, c);
-        batch_unref(R->batch);
-    }
+    (void)hipSetDevice(R->c->device);
+    R->lz.orphan(R->c->pq, map_check, 0, R->hitf); /* index and batch stay until the kernels have run: they read d_seq_len */
     if (R->reads) sketch_unref(R->reads);
     delete R;
 }
@@ -2260,33 +2159,30 @@ static void mapres_free(ntl_mapres *R)
 static int mapres_finalize(const ntl_mapres *cR)
 {
     ntl_mapres *R = const_cast<ntl_mapres *>(cR);
-    if (!R->pending) return R->failed;
+    Pending &lz = R->lz;
+    if (!lz.pending) return lz.failed;
     ntl_ctx *c = R->c;
     (void)hipSetDevice(c->device);
     for (int round = 0;; round++) {
-        if (R->reads && (R->failed = sketch_finalize(R->reads))) { (void)hipEventSynchronize(R->done); R->pending = false; break; }
-        const hipError_t e = wait_hot(R->done);
-        R->pending = false;
-        if (e != hipSuccess) { R->failed = fail(c, NTL_EDEVICE, std::string("map: ") + hipGetErrorString(e)); break; }
+        if (R->reads && (lz.failed = sketch_finalize(R->reads))) { (void)hipEventSynchronize(lz.done); lz.pending = false; break; }
+        const hipError_t e = lz.wait();
+        lz.pending = false;
+        if (e != hipSuccess) { lz.failed = fail(c, NTL_EDEVICE, std::string("map: ") + hipGetErrorString(e)); break; }
         if (R->reads && R->reads->gen != R->reads_gen && round == 0) {
-            memset(R->slot, 0, sizeof(PinSlot));
-            const int rc = map_enqueue(c, R->ix, R->reads, R->d_rlen, R);
-            if (rc) { (void)sync_both(c); map_scrub(c, R); R->pending = false; R->failed = rc; break; }
+            memset(lz.slot, 0, sizeof(PinSlot));
+            const int rc = map_enqueue(c, (const ntl_index *)lz.holds[0].p, R->reads, R->d_rlen, R);
+            if (rc) { pending_abort(c, lz, rc, true); break; }
             continue;
         }
-        const MapSums hs = *(const MapSums *)R->slot;
+        const MapSums hs = *(const MapSums *)lz.slot;
         R->n_maps = hs.tot[0]; R->n_hits = hs.tot[1]; R->n_pafs = hs.tot[2];
         R->n_index_hits = hs.nfound;
-        if (hs.nmx) R->hitf->store((float)((double)hs.nfound / (double)hs.nmx), std::memory_order_relaxed);
-        if (hs.err) R->failed = fail(c, NTL_EINTERNAL, "an accepted contig appeared twice in one read (bin/ntlink_utils.py:262-266)");
+        if (const char *m = map_check(*lz.slot, 0, R->hitf.get())) lz.failed = fail(c, NTL_EINTERNAL, m);
         break;
     }
     if (R->reads) { sketch_unref(R->reads); R->reads = nullptr; }
-    index_unref(R->ix, c); R->ix = nullptr;
-    batch_unref(R->batch); R->batch = nullptr;
-    sev_put(c, R->done); R->done = nullptr;
-    slot_put(c, R->slot); R->slot = nullptr;
-    return R->failed;
+    lz.settle(c->pq);
+    return lz.failed;
 }
 
 extern "C" int ntl_map_run(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads, const uint32_t *read_len,
@@ -2301,11 +2197,10 @@ extern "C" int ntl_map_run(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *re
     }
     const uint64_t nreads = reads->nseq;
     ntl_mapres *R = new ntl_mapres();
-    R->c = c; R->ix = ix; R->params = *params; R->hitf = ix->hit_fraction;
+    R->c = c; R->params = *params; R->hitf = ix->hit_fraction;
     ix->refs++;
-    R->done = sev_get(c);
-    R->slot = slot_get(c);
-    if (!R->done || !R->slot) { mapres_free(R); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
+    R->lz.holds[0] = {ix, hold_index};
+    if (!R->lz.arm(c->pq)) { mapres_free(R); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
     int rc = NTL_OK;
     /* read lengths: a sketch made from a batch that it still holds (pending) reads them from the batch (the `--len` column IS the
        sequence length); the result holds the batch too, until its kernels have run (mapres_finalize, or reap for a result destroyed
@@ -2314,7 +2209,7 @@ extern "C" int ntl_map_run(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *re
     if (reads->src && reads->src->d_seq_len && nreads && memcmp(read_len, reads->src->seq_len.data(), nreads * 4) == 0) {
         d_rlen = reads->src->d_seq_len;
         const_cast<ntl_batch *>(reads->src)->refs++;
-        R->batch = reads->src;
+        R->lz.holds[1] = {reads->src, hold_batch};
     }
     if (!d_rlen) {
         if ((rc = R->rlen_own.alloc(c, (nreads + 1) * 4))) { mapres_free(R); return rc; }
@@ -2331,9 +2226,7 @@ extern "C" int ntl_map_run(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *re
     const_cast<ntl_sketch *>(reads)->refs++;
     R->reads = reads;
     if ((rc = map_enqueue(c, ix, reads, d_rlen, R))) {
-        (void)sync_both(c);
-        map_scrub(c, R);
-        R->pending = false;
+        pending_abort(c, R->lz, rc, true);
         mapres_free(R);
         return rc;
     }

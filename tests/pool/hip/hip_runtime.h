@@ -1,5 +1,6 @@
 /*
- * A scripted stand-in for the HIP runtime: only what ntlink_amd/csrc/dev_pool.h calls.  TEST TOOL ONLY (tests/pool/pool_check.cpp).
+ * A scripted stand-in for the HIP runtime: only what ntlink_amd/csrc/dev_pool.h and pending.h call.  TEST TOOL ONLY (tests/pool/pool_check.cpp,
+ * pending_check.cpp).
  *
  * Streams belong to the test: each has a count of queued and of completed work.  An event records its stream's queued count and has
  * passed once the completed count reaches it; the test advances completion by hand (a host-side wait advances it too, and is counted).
@@ -72,3 +73,4 @@ inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned)
     return hipSuccess;
 }
 inline hipError_t hipGetLastError() { return hipSuccess; }
+inline const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "scripted error"; }
