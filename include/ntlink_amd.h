@@ -21,6 +21,9 @@
  *                                                      get_accepted_anchor_contigs
  *                                                      (bin/ntlink_utils.py:200-294),
  *                                                      print_paf (bin/ntlink_paf_output.py:103-135)
+ *   ntl_map_run_grouped  every read looked up in    <- map_long_reads + read_btllib_minimizers
+ *                 the contigs of its own group only    (bin/ntlink_patch_gaps.py:397-442): per gap one read
+ *                                                      piece against its two scaffold ends
  *   ntl_fastx_*   FASTA/FASTQ(.gz) records          <- `gzip -cd -f FILES |` + SeqReader
  *                                                      (ntLink:113-117,222-223)
  *   ntl_tsv_*     indexlr TSV -> arrays             <- the split()s of bin/ntlink_pair.py:197-207,355-378
@@ -296,7 +299,7 @@ int ntl_map_run(ntl_ctx *ctx, const ntl_index *ix, const ntl_sketch *reads, cons
                 const ntl_map_params *params, ntl_mapres **out);
 void ntl_mapres_destroy(ntl_mapres *r);
 /* Waits until the result is complete; 0 or the error its completion met (NTL_EINTERNAL: the reference's assertion that every
- * accepted contig appears once per read, bin/ntlink_utils.py:262-266, failed). */
+ * accepted contig appears once per read, bin/ntlink_utils.py:262-266, failed; or a grouped result's table was sized wrongly). */
 int ntl_mapres_wait(const ntl_mapres *r);
 uint64_t ntl_mapres_n_mappings(const ntl_mapres *r);
 uint64_t ntl_mapres_n_hits(const ntl_mapres *r);
@@ -304,6 +307,26 @@ uint64_t ntl_mapres_n_pafs(const ntl_mapres *r);
 /* Number of read minimizers found in the index (before any filter): the hit fraction h. */
 uint64_t ntl_mapres_n_index_hits(const ntl_mapres *r);
 int ntl_mapres_download(const ntl_mapres *r, ntl_mapping *maps, ntl_hit *hits, ntl_paf *pafs);
+
+/* Grouped mapping: ntl_index_build + ntl_map_run once per group, on that group's contigs and reads alone, in one device pass -- the
+ * gap filler's re-mapping loop (map_long_reads, bin/ntlink_patch_gaps.py:412-442: per gap one read piece against the minimizer dict
+ * of the two scaffold ends around it, read_btllib_minimizers :397-410).  Group g = the contigs [ctg_group_off[g], ctg_group_off[g+1])
+ * of the contig sketch and the reads [read_group_off[g], read_group_off[g+1]) of the read sketch; both arrays hold n_groups + 1
+ * entries, start at 0, do not decrease and end at their sketch's nseq (anything else: NTL_EINVAL); a group may have no contigs, no
+ * reads, or neither.  A hash that occurs more than once among ONE group's contig minimizers is dropped for that group; the same hash
+ * in two groups is kept in both; a read minimizer is looked up in its own group only.  The result is an ordinary ntl_mapres: read and
+ * contig numbers are those of the two sketches (not per group), order is read order, n_index_hits is the sum over the groups, and
+ * every ntl_mapres_* call works on it.  ctg_len[contig nseq] (fewer than 2^29 contigs), read_len[read nseq].  Both sketches must hold
+ * records (one made by ntl_sketch_run_for_map: NTL_EINVAL).  The call completes the two sketches first (a host wait: their counts
+ * size the work); the result is pending like any map result, and both sketches and all arrays may go as soon as the call returns. */
+int ntl_map_run_grouped(ntl_ctx *ctx, const ntl_sketch *contigs, const uint32_t *ctg_len, const uint32_t *ctg_group_off,
+                        const ntl_sketch *reads, const uint32_t *read_len, const uint32_t *read_group_off, uint32_t n_groups,
+                        const ntl_map_params *params, ntl_mapres **out);
+/* Diagnostics of a grouped result: a group with n contig minimizers keeps its table (the smallest power of two >= max(1024, 2 n + 2)
+ * slots) in the workgroup's LDS when that is at most lds_slots, otherwise in global scratch memory (the result is the same either
+ * way).  NTL_EINVAL for an ordinary result. */
+typedef struct { uint32_t lds_slots; uint64_t groups_in_lds, groups_in_global; } ntl_grouped_info;
+int ntl_mapres_grouped_info(const ntl_mapres *r, ntl_grouped_info *out);
 
 /* ---- host-side native I/O (no GPU involved) ------------------------------------------------ */
 

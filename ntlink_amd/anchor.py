@@ -16,8 +16,9 @@ return shape, computed by the pair stage's map kernel through the C ABI:
 * returns           ({contig: ContigRun}, [contig, ...]) with ``ContigRun.hits`` a list of
                     ``MinimizerPositions(mx, ctg_pos, ctg_strand, read_pos, read_strand)``
 
-One call costs a few device round trips, which is fine for the thousands of gaps of an assembly;
-`AnchorMapper.map_many` batches reads that share an index.
+One call costs two sketch uploads, an index build, a map and a download.  `AnchorMapper.map_many` batches
+reads that share an index; the gap filler's loop, where every read has an index of its own (10^4 - 10^5
+gaps per round), is `ntlink_amd.gapfill.map_gap_reads`: all gaps in one grouped device pass.
 """
 from collections import namedtuple
 

@@ -26,7 +26,7 @@ SYMBOLS = [
     "ntl_sketch_from_host", "ntl_overlap_filter",
     "ntl_index_build", "ntl_index_destroy", "ntl_index_size",
     "ntl_map_run", "ntl_mapres_destroy", "ntl_mapres_n_mappings", "ntl_mapres_n_hits", "ntl_mapres_n_pafs",
-    "ntl_mapres_n_index_hits", "ntl_mapres_download",
+    "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_map_run_grouped", "ntl_mapres_grouped_info",
     "ntl_fastx_open", "ntl_fastx_open_range", "ntl_fastx_range", "ntl_fastx_close", "ntl_fastx_error", "ntl_fastx_next", "ntl_fastx_sizes", "ntl_fastx_copy", "ntl_fastx_copy_packed", "ntl_fastx_runs", "ntl_fastx_next_span", "ntl_fastx_parse_span", "ntl_fastx_copy_span", "ntl_fastx_seqs", "ntl_fastx_offsets",
     "ntl_fastx_names", "ntl_fastx_name_offsets", "ntl_write_indexlr", "ntl_write_verbose", "ntl_write_paf",
     "ntl_tsv_open", "ntl_tsv_close", "ntl_tsv_error", "ntl_tsv_next", "ntl_tsv_sizes", "ntl_tsv_copy",
@@ -52,6 +52,11 @@ class PlanInfo(C.Structure):
     """ntl_plan_info"""
     _fields_ = [(nm, C.c_int32) for nm in ("pass", "nt", "C", "NWO", "big", "direct", "wave_wavefronts", "wave_slots", "wave_rounds",
                                            "wave_kmers", "lists")] + [("thresh", C.c_uint32)]
+
+
+class GroupedInfo(C.Structure):
+    """ntl_grouped_info"""
+    _fields_ = [("lds_slots", C.c_uint32), ("groups_in_lds", C.c_uint64), ("groups_in_global", C.c_uint64)]
 
 
 PASSES = ("small", "exact_only", "block_minima", "thresh", "wave")  # NTL_PASS_*
@@ -138,6 +143,8 @@ def load(path=None):
     L.ntl_index_size.argtypes = [vp]
     L.ntl_index_size.restype = C.c_uint64
     L.ntl_map_run.argtypes = [vp, vp, vp, u32p, C.POINTER(MapParams), C.POINTER(vp)]
+    L.ntl_map_run_grouped.argtypes = [vp, vp, u32p, u32p, vp, u32p, u32p, C.c_uint32, C.POINTER(MapParams), C.POINTER(vp)]
+    L.ntl_mapres_grouped_info.argtypes = [vp, C.POINTER(GroupedInfo)]
     L.ntl_mapres_destroy.argtypes = [vp]
     L.ntl_mapres_destroy.restype = None
     for nm in ("n_mappings", "n_hits", "n_pafs", "n_index_hits"):
@@ -341,6 +348,14 @@ class MapResult(_Handle):
     def n_index_hits(self):
         self.wait()
         return int(self.dev.L.ntl_mapres_n_index_hits(self.ptr))
+
+    @property
+    def grouped_info(self):
+        """Of a result of Device.map_grouped (ntl_mapres_grouped_info; diagnostics): dict(lds_slots=, groups_in_lds=, groups_in_global=)
+        -- where the groups' tables lived.  An ordinary result raises."""
+        info = GroupedInfo()
+        self.dev._chk(self.dev.L.ntl_mapres_grouped_info(self.ptr, C.byref(info)))
+        return {"lds_slots": int(info.lds_slots), "groups_in_lds": int(info.groups_in_lds), "groups_in_global": int(info.groups_in_global)}
 
     def counts(self):
         self.wait()
@@ -641,4 +656,22 @@ class Device:
         p = C.c_void_p()
         self._chk(self.L.ntl_map_run(self.ptr, index.ptr, read_sketch.ptr, _ptr(rl, C.c_uint32), C.byref(P),
                                      C.byref(p)))
+        return MapResult(self, p)
+
+    def map_grouped(self, contig_sketch, ctg_len, ctg_group_off, read_sketch, read_len, read_group_off, k, z=1000, x=0.0, sensitive=False,
+                    repeat_filter=False):
+        """Device.index + Device.map once per group, in one device pass (ntl_map_run_grouped): group g = the contigs
+        [ctg_group_off[g], ctg_group_off[g+1]) and the reads [read_group_off[g], read_group_off[g+1]); a hash that occurs twice among
+        one group's contigs is dropped for that group only, a read is looked up in its own group only.  Contig and read numbers of the
+        result are those of the two sketches.  Both sketches and every array may go once this returns."""
+        cl = np.ascontiguousarray(ctg_len, np.uint32); rl = np.ascontiguousarray(read_len, np.uint32)
+        co = np.ascontiguousarray(ctg_group_off, np.uint32); ro = np.ascontiguousarray(read_group_off, np.uint32)
+        if len(cl) != contig_sketch.nseq or len(rl) != read_sketch.nseq:
+            raise ValueError("ctg_len / read_len must have one entry per sketched sequence")
+        if len(co) != len(ro) or len(co) < 1:
+            raise ValueError("the group offsets must have n_groups + 1 entries each")
+        P = MapParams(int(k), int(z), float(x), int(bool(sensitive)), int(bool(repeat_filter)))
+        p = C.c_void_p()
+        self._chk(self.L.ntl_map_run_grouped(self.ptr, contig_sketch.ptr, _ptr(cl, C.c_uint32), _ptr(co, C.c_uint32), read_sketch.ptr,
+                                             _ptr(rl, C.c_uint32), _ptr(ro, C.c_uint32), len(co) - 1, C.byref(P), C.byref(p)))
         return MapResult(self, p)

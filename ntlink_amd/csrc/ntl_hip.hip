@@ -31,6 +31,7 @@
 #include "sketch_small_kernels.h"
 #include "window_plan.h"
 #include "map_kernels.h"
+#include "group_kernels.h"
 #include "pack_kernels.h"
 #include "synth_kernels.h"
 #include "overlap_kernels.h"
@@ -2029,14 +2030,26 @@ struct ntl_mapres {
     std::shared_ptr<std::atomic<float>> hitf; /* the index's hit fraction (the index itself may be gone when this completes) */
     DevBuf rlen_own;                    /* read lengths uploaded by this call (sketches that did not come from a batch) */
     const uint32_t *d_rlen = nullptr;   /* the read lengths the kernels read: rlen_own, or the batch's own (d_seq_len; lz holds the batch) */
+    /* ntl_map_run_grouped: no index; lz.holds[0] is the CONTIG SKETCH (the lookup reads its records), the contig lengths are the result's own */
+    bool grouped = false;
+    ntl_grouped_info ginfo = {};
+    DevBuf ctg_len_own;
+};
+
+/* what map_enqueue queues in place of the index lookup for a grouped result (group_kernels.h) */
+struct GroupJob {
+    GroupArgs A;               /* cand, rpos, nfound and err are map_enqueue's to fill in */
+    const uint32_t *d_ctg_len; /* MapArgs::ctg_len: the result's own copy */
+    unsigned grid;
 };
 
 /* Queues the lookup (when the sketch does not carry candidates), the map kernels, the offset scans and the gather on MAIN.
  * Nothing waits: the three totals, the hit count and the invariant flag land in the result's page-locked slot. */
-static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads, const uint32_t *d_rlen, ntl_mapres *R)
+static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads, const uint32_t *d_rlen, ntl_mapres *R,
+                       const GroupJob *gj = nullptr)
 {
     const uint64_t nreads = reads->nseq;
-    const bool have_cand = reads->cand_gen == ix->gen && reads->cand.p != nullptr;
+    const bool have_cand = !gj && reads->cand_gen == ix->gen && reads->cand.p != nullptr;
     if (reads->no_records && !have_cand) return fail(c, NTL_EINVAL, "a sketch made by ntl_sketch_run_for_map maps against the index it was made for only");
     if (!have_cand) { /* the lookup pass runs over the records: their number sizes its grid */
         if (int frc = sketch_finalize(reads)) return frc;
@@ -2060,10 +2073,16 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
        (or, on the error paths, after pending_abort zeroed it) -- and every kernel that adds to it runs on MAIN behind the gather of the slot's
        previous holder.  The lookup's count of a sketch made for this index stays where the lookup left it (SketchSums::nfound). */
     MapSums *dsums = (MapSums *)c->pq.slot_dsums(R->lz.slot);
-    if (ix->c != c && ix->built) HIPCHK(c, hipStreamWaitEvent(ms, ix->built, 0));
+    if (ix && ix->c != c && ix->built) HIPCHK(c, hipStreamWaitEvent(ms, ix->built, 0));
     if (!have_cand) {
         ProfSpan sp(c, "probe");
-        if (nmx) {
+        if (gj) { /* every read in the contigs of its own group: tables built, used and dropped by one kernel */
+            if (nmx) {
+                GroupArgs G = gj->A;
+                G.cand = cand.as<Cand>(); G.rpos = rpos.as<uint32_t>(); G.nfound = &dsums->nfound; G.err = &dsums->err;
+                hipLaunchKernelGGL(group_probe_kernel, dim3(gj->grid), dim3(GROUP_NT), 0, ms, G);
+            }
+        } else if (nmx) {
             const dim3 grid((unsigned)std::min<uint64_t>((nmx + 256 * PROBE_U - 1) / (256 * PROBE_U), 4096));
             /* tags first unless the previous batch on this index found more than half of its minimizers (same result either way) */
             if (ix->hit_fraction->load(std::memory_order_relaxed) <= 0.5f)
@@ -2083,7 +2102,7 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
     A.mx_off = reads->mx_off.as<uint32_t>();
     A.rpos = have_cand ? reads->rpos.as<uint32_t>() : rpos.as<uint32_t>();
     A.cand = have_cand ? reads->cand.as<Cand>() : cand.as<Cand>();
-    A.read_len = d_rlen; A.ctg_len = ix->ctg_len.as<uint32_t>(); A.nreads = (uint32_t)nreads;
+    A.read_len = d_rlen; A.ctg_len = gj ? gj->d_ctg_len : ix->ctg_len.as<uint32_t>(); A.nreads = (uint32_t)nreads;
     A.P.k = params->k; A.P.z = params->z; A.P.x = params->x; A.P.sensitive = params->sensitive;
     A.P.repeat_filter = params->repeat_filter;
     A.maps = smaps.as<MapRec>(); A.hits = R->hits.as<HitRec>(); A.pafs = spafs.as<PafRec>();
@@ -2142,6 +2161,7 @@ static const char *map_check(const PinSlot &slot, uint64_t, std::atomic<float> *
 {
     const MapSums &hs = (const MapSums &)slot;
     if (hitf && hs.nmx) hitf->store((float)((double)hs.nfound / (double)hs.nmx), std::memory_order_relaxed);
+    if (hs.err & GROUP_ERR_PROBE) return "a probe sequence of a grouped lookup did not end within its table (group_kernels.h)";
     return hs.err ? "an accepted contig appeared twice in one read (bin/ntlink_utils.py:262-266)" : nullptr;
 }
 
@@ -2240,6 +2260,110 @@ extern "C" uint64_t ntl_mapres_n_mappings(const ntl_mapres *r) { return r && map
 extern "C" uint64_t ntl_mapres_n_hits(const ntl_mapres *r) { return r && mapres_finalize(r) == NTL_OK ? r->n_hits : 0; }
 extern "C" uint64_t ntl_mapres_n_pafs(const ntl_mapres *r) { return r && mapres_finalize(r) == NTL_OK ? r->n_pafs : 0; }
 extern "C" uint64_t ntl_mapres_n_index_hits(const ntl_mapres *r) { return r && mapres_finalize(r) == NTL_OK ? r->n_index_hits : 0; }
+
+/* ------------------------------------------------------------------ grouped map ---------- */
+
+static void hold_sketch(const void *s, void *) { sketch_unref((const ntl_sketch *)s); }
+
+static const char *group_offsets_check(const uint32_t *off, uint32_t n_groups, uint64_t nseq, const char *what, std::string &msg)
+{
+    if (off[0] != 0) msg = std::string(what) + "[0] must be 0";
+    else if (off[n_groups] != nseq) msg = std::string(what) + " must end at the sketch's number of sequences";
+    else
+        for (uint32_t g = 0; g < n_groups; g++)
+            if (off[g + 1] < off[g]) { msg = std::string(what) + " must be non-decreasing"; break; }
+    return msg.empty() ? nullptr : msg.c_str();
+}
+
+extern "C" int ntl_map_run_grouped(ntl_ctx *c, const ntl_sketch *ctg, const uint32_t *ctg_len, const uint32_t *ctg_group_off,
+                                   const ntl_sketch *reads, const uint32_t *read_len, const uint32_t *read_group_off, uint32_t n_groups,
+                                   const ntl_map_params *params, ntl_mapres **out)
+{
+    if (!c || !ctg || !reads || !params || !out || !ctg_group_off || !read_group_off || (!ctg_len && ctg->nseq) ||
+        (!read_len && reads->nseq)) return NTL_EINVAL;
+    *out = nullptr;
+    (void)hipSetDevice(c->device);
+    if (ctg->no_records || reads->no_records) return fail(c, NTL_EINVAL, "a sketch made by ntl_sketch_run_for_map holds no records");
+    if (ctg->nseq >= (1u << 29)) return fail(c, NTL_EINVAL, "too many contigs"); /* contig id << 3 | flags in one word (map_kernels.h) */
+    if (n_groups == 0xFFFFFFFFu) return fail(c, NTL_EINVAL, "too many groups");
+    std::string msg;
+    if (group_offsets_check(ctg_group_off, n_groups, ctg->nseq, "ctg_group_off", msg) ||
+        group_offsets_check(read_group_off, n_groups, reads->nseq, "read_group_off", msg)) return fail(c, NTL_EINVAL, msg);
+    /* the counts size the work: the tables from the contig minimizers, the lookup's arrays from the reads' */
+    if (int frc = sketch_finalize(ctg)) return frc;
+    if (int frc = sketch_finalize(reads)) return frc;
+    if (ctg->c != c) HIPCHK(c, sync_both(ctg->c));
+    if (reads->c != c) HIPCHK(c, sync_both(reads->c));
+    /* a large group's table has fewer than 4 n + 4 slots (at least 1024): all regions together must fit the 32-bit scan */
+    if (4ull * ctg->count + 1024ull * n_groups >= 0xFFFFFFF0ull) return fail(c, NTL_EINVAL, "too many contig minimizers for one grouped call");
+    const uint64_t n_ctg = ctg->nseq, nreads = reads->nseq;
+    ntl_mapres *R = new ntl_mapres();
+    R->c = c; R->params = *params; R->grouped = true;
+    if (!R->lz.arm(c->pq)) { mapres_free(R); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
+    const_cast<ntl_sketch *>(ctg)->refs++;
+    R->lz.holds[0] = {ctg, hold_sketch};
+    const_cast<ntl_sketch *>(reads)->refs++;
+    R->reads = reads;
+    int rc = NTL_OK;
+    DevBuf cg, rg, big, boff, next, scratch;
+    const uint64_t ng1 = (uint64_t)n_groups + 1;
+    if ((rc = R->ctg_len_own.alloc(c, (n_ctg + 1) * 4)) || (rc = R->rlen_own.alloc(c, (nreads + 1) * 4)) || (rc = cg.alloc(c, ng1 * 4)) ||
+        (rc = rg.alloc(c, ng1 * 4)) || (rc = big.alloc(c, 2 * ng1 * 4)) || (rc = boff.alloc(c, 2 * ng1 * 4)) || (rc = next.alloc(c, 4))) {
+        pending_abort(c, R->lz, rc);
+        mapres_free(R);
+        return rc;
+    }
+    auto bail = [&](int code, const std::string &m) {
+        pending_abort(c, R->lz, code, true);
+        mapres_free(R);
+        return fail(c, code, m);
+    };
+    {
+        hipError_t e = hipSuccess;
+        if (n_ctg) e = hipMemcpyAsync(R->ctg_len_own.p, ctg_len, n_ctg * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess && nreads) e = hipMemcpyAsync(R->rlen_own.p, read_len, nreads * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(cg.p, ctg_group_off, ng1 * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemcpyAsync(rg.p, read_group_off, ng1 * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(next.p, 0, 4, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(big.p, 0, 2 * ng1 * 4, c->stream);
+        if (e != hipSuccess) return bail(NTL_EDEVICE, "upload of the lengths and group offsets failed");
+    }
+    R->d_rlen = R->rlen_own.as<uint32_t>();
+    GroupJob J;
+    memset(&J, 0, sizeof J);
+    J.A.cmx = ctg->records.as<MxRecord>(); J.A.c_off = ctg->mx_off.as<uint32_t>();
+    J.A.rmx = reads->records.as<MxRecord>(); J.A.r_off = reads->mx_off.as<uint32_t>();
+    J.A.cg_off = cg.as<uint32_t>(); J.A.rg_off = rg.as<uint32_t>(); J.A.n_groups = n_groups;
+    J.A.big_off = boff.as<uint32_t>(); J.A.next = next.as<uint32_t>();
+    J.d_ctg_len = R->ctg_len_own.as<uint32_t>();
+    /* regions of the large groups: one scan over their slot counts and one over a 1 per large group; the two totals are the call's
+       one size that comes back (behind it the caller's arrays are free again, too) */
+    uint32_t totals[2] = {0, 0};
+    if (n_groups) {
+        hipLaunchKernelGGL(group_size_kernel, dim3((n_groups + 255) / 256), dim3(256), 0, c->stream, J.A, big.as<uint32_t>());
+        if (hipGetLastError() != hipSuccess) return bail(NTL_EDEVICE, "group_size_kernel could not be launched");
+    }
+    if (n_groups) {
+        if ((rc = device_scan(c, big.as<uint32_t>(), boff.as<uint32_t>(), n_groups, totals, 2))) return bail(rc, c->err);
+    } else if (hipStreamSynchronize(c->stream) != hipSuccess) return bail(NTL_EDEVICE, "upload of the lengths and group offsets failed");
+    R->ginfo.lds_slots = GROUP_LDS_SLOTS;
+    R->ginfo.groups_in_global = totals[1];
+    R->ginfo.groups_in_lds = (uint64_t)n_groups - totals[1];
+    if ((rc = scratch.alloc(c, ((uint64_t)totals[0] + 1) * sizeof(IndexSlot)))) return bail(rc, c->err);
+    J.A.scratch = scratch.as<IndexSlot>();
+    static const int per_cu = occupancy_blocks(group_probe_kernel, GROUP_NT);
+    J.grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_groups, (uint64_t)per_cu * (uint64_t)std::max(1, c->n_cu)));
+    if ((rc = map_enqueue(c, nullptr, reads, R->d_rlen, R, &J))) return bail(rc, c->err);
+    *out = R;
+    return NTL_OK;
+}
+
+extern "C" int ntl_mapres_grouped_info(const ntl_mapres *r, ntl_grouped_info *out)
+{
+    if (!r || !out || !r->grouped) return NTL_EINVAL;
+    *out = r->ginfo;
+    return NTL_OK;
+}
 
 /* hit_doff[m] = hits of the mappings before m (the dense numbering of the hits); needs a completed result */
 static int mapres_dense_offsets(const ntl_mapres *r)

@@ -1,0 +1,180 @@
+"""The gap filler's re-mapping loop in one device pass.
+
+`map_long_reads` of the reference (bin/ntlink_patch_gaps.py:412-442) reads two temporary FASTA files in lockstep -- per gap one chosen
+read piece and the two masked scaffold ends around the gap -- and per gap builds a minimizer dict of the two scaffold records alone
+(read_btllib_minimizers, :397-410: a hash seen twice among the two is dropped), keeps the read's minimizers that are in it and calls
+get_accepted_anchor_contigs.  Here all gaps of a batch are sketched together and mapped by ONE grouped call
+(Device.map_grouped, ntl_map_run_grouped: gap g = group g, its contigs the records 2g and 2g+1, its read the record g):
+
+    for gap in gapfill.map_gap_reads(scaffolds_fasta, reads_fasta, k, w, args):
+        gap.read, gap.source, gap.target     # btllib-compatible records: .id .readlen .num (+ .minimizers with with_minimizers=True)
+        gap.accepted, gap.order              # what get_accepted_anchor_contigs returns for this gap
+
+* read record i belongs with the scaffold records 2i (source) and 2i+1 (target)
+* the keys of ``accepted`` and ``ContigRun.contig`` are contig NAMES: ``name_of(record_id)``, by default the record id without its
+  trailing ``_source`` / ``_target`` and without ``+`` / ``-`` at either end (what :415,426-433 make of it)
+* a gap whose two names come out equal takes the single-index path (anchor.AnchorMapper), where the two records share one contig as
+  they do in the reference's dict; the grouped call keeps two contigs apart
+* contig lengths are the records' lengths: the reference's temporary files hold every scaffold N-masked to its full length
+* ``args`` needs ``.k .z .x .sensitive``; ``MinimizerPositions.mx`` is the hash as ``str``
+"""
+import re
+
+import numpy as np
+
+from . import anchor, seqio
+from .anchor import ContigRun, Minimizer, MinimizerPositions
+
+_STRAND = ("-", "+")
+_LABEL = re.compile(r"_(source|target)$")
+BATCH_BASES = 256 << 20  # bases of scaffold and read records per device pass (a gap is never split)
+
+
+def default_name_of(record_id):
+    """`scaf12+_source` -> `scaf12`"""
+    return _LABEL.sub("", record_id).strip("+-")
+
+
+class SketchMinimizer:
+    """One minimizer of a record, with btllib's field names."""
+    __slots__ = ("out_hash", "pos", "forward")
+
+    def __init__(self, out_hash, pos, forward):
+        self.out_hash, self.pos, self.forward = out_hash, pos, forward
+
+
+class Record:
+    """What btllib.Indexlr yields, as far as map_long_reads reads it."""
+    __slots__ = ("id", "readlen", "num", "minimizers")
+
+    def __init__(self, id, readlen, num, minimizers=None):
+        self.id, self.readlen, self.num, self.minimizers = id, readlen, num, minimizers
+
+
+class Gap:
+    __slots__ = ("read", "source", "target", "accepted", "order")
+
+    def __init__(self, read, source, target, accepted, order):
+        self.read, self.source, self.target, self.accepted, self.order = read, source, target, accepted, order
+
+
+class _Length:
+    def __init__(self, length):
+        self.length = length
+
+
+def _minimizers(sk, i):
+    off, h, p, s = sk
+    a, b = int(off[i]), int(off[i + 1])
+    return [SketchMinimizer(int(h[j]), int(p[j]), bool(s[j])) for j in range(a, b)]
+
+
+def _single_index_gap(dev, ssk, rsk, g, name, ctg_len, read_len, args):
+    """read_btllib_minimizers + get_accepted_anchor_contigs for a gap whose two records carry one contig name"""
+    off, h, p, s = ssk
+    mx_info, dup = {}, set()
+    for j in range(int(off[2 * g]), int(off[2 * g + 2])):
+        key = str(int(h[j]))
+        if key in mx_info:
+            dup.add(key)
+        else:
+            mx_info[key] = Minimizer(name, int(p[j]), _STRAND[int(s[j])])
+    for key in dup:
+        del mx_info[key]
+    roff, rh, rp, rs = rsk
+    mxs = [(str(int(rh[j])), int(rp[j]), _STRAND[int(rs[j])]) for j in range(int(roff[g]), int(roff[g + 1])) if str(int(rh[j])) in mx_info]
+    return anchor.get_accepted_anchor_contigs(mxs, read_len, {name: _Length(ctg_len)}, mx_info, args, dev=dev)
+
+
+def _map_batch(dev, scaffolds, reads, first, k, w, args, with_minimizers, name_of):
+    """one device pass over len(reads) gaps; `first`: the number of the batch's first read record"""
+    n = len(reads)
+    names = [name_of(sid) for sid, _seq in scaffolds]
+    equal = [g for g in range(n) if names[2 * g] == names[2 * g + 1]]
+    ctg_len = np.fromiter((len(seq) for _id, seq in scaffolds), np.uint32, 2 * n)
+    read_len = np.fromiter((len(seq) for _id, seq in reads), np.uint32, n)
+    with dev.batch([bytes(seq) for _id, seq in scaffolds]) as sb, dev.batch([bytes(seq) for _id, seq in reads]) as rb, \
+            dev.sketch(sb, k, w) as ssk, dev.sketch(rb, k, w) as rsk:
+        with dev.map_grouped(ssk, ctg_len, 2 * np.arange(n + 1, dtype=np.uint32), rsk, read_len, np.arange(n + 1, dtype=np.uint32),
+                             k=int(args.k), z=int(args.z), x=float(args.x), sensitive=bool(args.sensitive)) as res:
+            rec = res.download()
+        rmx = rsk.download()
+        smx = ssk.download() if with_minimizers or equal else None
+    maps, hits = rec["maps"], rec["hits"]
+    # the hash of a hit: the read's record at that position (positions ascend within a read, reads are in order: one sorted key)
+    roff, rh, rp, _rs = rmx
+    read_of_mx = np.repeat(np.arange(n, dtype=np.uint64), np.diff(roff).astype(np.int64))
+    mx_key = (read_of_mx << np.uint64(32)) | rp.astype(np.uint64)
+    hit_read = np.repeat(maps["read"].astype(np.uint64), maps["n_hits"].astype(np.int64))
+    where = np.searchsorted(mx_key, (hit_read << np.uint64(32)) | hits["read_pos"].astype(np.uint64))
+    hit_hash = rh[where] if len(hits) else np.empty(0, np.uint64)
+    accepted = [({}, []) for _ in range(n)]
+    h_pos, h_rpos = hits["ctg_pos"].tolist(), hits["read_pos"].tolist()
+    h_cs, h_rs, h_mx = hits["ctg_strand"].tolist(), hits["read_strand"].tolist(), hit_hash.tolist()
+    for r, c, nh, ho in zip(maps["read"].tolist(), maps["ctg"].tolist(), maps["n_hits"].tolist(), maps["hit_off"].tolist()):
+        name = names[c]
+        run = ContigRun(name, [MinimizerPositions(mx=str(h_mx[j]), ctg_pos=h_pos[j], ctg_strand=_STRAND[h_cs[j]], read_pos=h_rpos[j],
+                                                  read_strand=_STRAND[h_rs[j]]) for j in range(ho, ho + nh)])
+        accepted[r][0][name] = run
+        accepted[r][1].append(name)
+    for g in equal:
+        accepted[g] = _single_index_gap(dev, smx, rmx, g, names[2 * g], int(ctg_len[2 * g]), int(read_len[g]), args)
+    for g in range(n):
+        recs = [Record(reads[g][0], int(read_len[g]), first + g),
+                Record(scaffolds[2 * g][0], int(ctg_len[2 * g]), 2 * (first + g)),
+                Record(scaffolds[2 * g + 1][0], int(ctg_len[2 * g + 1]), 2 * (first + g) + 1)]
+        if with_minimizers:
+            recs[0].minimizers = _minimizers(rmx, g)
+            recs[1].minimizers, recs[2].minimizers = _minimizers(smx, 2 * g), _minimizers(smx, 2 * g + 1)
+        yield Gap(recs[0], recs[1], recs[2], accepted[g][0], accepted[g][1])
+
+
+def _map_records(scaffolds, reads, k, w, args, dev, with_minimizers, name_of, batch_bases):
+    """scaffolds, reads: iterators of (id, sequence bytes); batches bounded by bases, a gap never split"""
+    dev = dev or anchor._default_device()
+    scaffolds, reads = iter(scaffolds), iter(reads)
+    first, sb, rb, bases = 0, [], [], 0
+
+    def flush():
+        nonlocal first, sb, rb, bases
+        yield from _map_batch(dev, sb, rb, first, k, w, args, with_minimizers, name_of)
+        first += len(rb)
+        sb, rb, bases = [], [], 0
+
+    for read in reads:
+        pair = [next(scaffolds, None), next(scaffolds, None)]
+        if pair[1] is None:
+            raise ValueError("fewer than two scaffold records per read record")
+        add = len(read[1]) + len(pair[0][1]) + len(pair[1][1])
+        if rb and bases + add > batch_bases:
+            yield from flush()
+        rb.append(read); sb += pair; bases += add
+    if next(scaffolds, None) is not None:
+        raise ValueError("more than two scaffold records per read record")
+    if rb:
+        yield from flush()
+
+
+def map_gap_sequences(scaffolds, reads, k, w, args, dev=None, with_minimizers=False, name_of=default_name_of, batch_bases=BATCH_BASES):
+    """The in-memory form: scaffolds = [(id, sequence)] (two per gap: source, target), reads = [(id, sequence)]; sequences as bytes or
+    str.  Yields one Gap per read record, in order."""
+    scaffolds, reads = list(scaffolds), list(reads)
+    if len(scaffolds) != 2 * len(reads):
+        raise ValueError(f"{len(scaffolds)} scaffold records for {len(reads)} read records: two per read are needed")
+    enc = lambda recs: ((i, s.encode() if isinstance(s, str) else s) for i, s in recs)
+    return _map_records(enc(scaffolds), enc(reads), k, w, args, dev, with_minimizers, name_of, batch_bases)
+
+
+def _records_of(path, batch_bases):
+    for ss in seqio.load(path, max_bases=batch_bases):
+        off = ss.offsets.tolist()
+        for i, name in enumerate(ss.names):
+            yield name, ss.buf[off[i]:off[i + 1]]
+
+
+def map_gap_reads(scaffolds_fasta, reads_fasta, k, w, args, dev=None, with_minimizers=False, name_of=default_name_of,
+                  batch_bases=BATCH_BASES):
+    """The loop header of map_long_reads over its two temporary files (<o>.scaffolds.masked_temp.fa, <o>.reads.masked_temp.fa).
+    A scaffold count other than twice the read count raises ValueError."""
+    return _map_records(_records_of(scaffolds_fasta, batch_bases), _records_of(reads_fasta, batch_bases), k, w, args, dev,
+                        with_minimizers, name_of, batch_bases)
