@@ -721,10 +721,14 @@ struct MapSumsOut {
     unsigned long long *sk_nfound;      /* not NULL: the read sketch's slot word for its hit count, too */
 };
 
-__global__ void map_gather_kernel(MapArgs A, const uint32_t *off_maps, const uint32_t *off_pafs, MapRec *d_maps, PafRec *d_pafs, MapSumsOut O)
+#define GATHER_NT 256
+
+/* A lane per read (most reads have no record, few have more than two: a workgroup per read spent its time being dispatched); a read
+   with several records copies them one after the other. */
+__global__ __launch_bounds__(GATHER_NT) void map_gather_kernel(MapArgs A, const uint32_t *off_maps, const uint32_t *off_pafs, MapRec *d_maps, PafRec *d_pafs, MapSumsOut O)
 {
-    const uint32_t r = blockIdx.x;
-    if (r == 0 && threadIdx.x == 0) { /* every kernel that writes the sums ran before this one */
+    const uint32_t r = blockIdx.x * GATHER_NT + threadIdx.x;
+    if (r == 0) { /* every kernel that writes the sums ran before this one */
         MapSums *d = O.sums;
         const unsigned long long nf = *O.nfound;
         const uint32_t nmx = map_sketch_overflowed(A) ? 0u : A.mx_off[A.nreads]; /* (an overflowed sketch: no hit fraction) */
@@ -735,16 +739,16 @@ __global__ void map_gather_kernel(MapArgs A, const uint32_t *off_maps, const uin
         if (O.sk_nfound) ntl_host_store64(O.sk_nfound, nf);
         d->nfound = 0ull; d->err = 0u; d->tot[0] = d->tot[1] = d->tot[2] = 0u; d->n_over = 0u; d->nmx = 0u;
     }
-    if (map_sketch_overflowed(A)) return;
+    if (r >= A.nreads || map_sketch_overflowed(A)) return;
     const uint32_t m0 = A.mx_off[r];
     const uint32_t nm = A.n_maps[r], npf = A.n_pafs[r];
     const uint32_t om = off_maps[r], op = off_pafs[r];
-    for (uint32_t i = threadIdx.x; i < nm; i += blockDim.x) {
+    for (uint32_t i = 0; i < nm; i++) {
         MapRec M = A.maps[m0 + i];
         M.hit_off += m0;
         d_maps[om + i] = M;
     }
-    for (uint32_t i = threadIdx.x; i < npf; i += blockDim.x) d_pafs[op + i] = A.pafs[m0 + i];
+    for (uint32_t i = 0; i < npf; i++) d_pafs[op + i] = A.pafs[m0 + i];
 }
 
 /* n_hits of every mapping as a u32 array (the input of the scan that numbers the hits densely) */

@@ -2140,7 +2140,7 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
         /* the sketch's own hit count, if nothing has copied it yet: its event moves behind this kernel (sketch_finalize waits for it) */
         O.sk_nfound = nullptr;
         if (have_cand && reads->lz.pending && reads->nfound_owed) O.sk_nfound = &((SketchSums *)c->pq.slot_dev(reads->lz.slot))->nfound;
-        hipLaunchKernelGGL(map_gather_kernel, dim3((unsigned)nreads), dim3(64), 0, ms, A, (const uint32_t *)o,
+        hipLaunchKernelGGL(map_gather_kernel, dim3((unsigned)((nreads + GATHER_NT - 1) / GATHER_NT)), dim3(GATHER_NT), 0, ms, A, (const uint32_t *)o,
                            (const uint32_t *)(o + 2 * (nreads + 1)), R->maps.as<MapRec>(), R->pafs.as<PafRec>(), O);
         HIPCHK(c, hipGetLastError());
         if (O.sk_nfound) {
