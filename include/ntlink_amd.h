@@ -24,6 +24,10 @@
  *   ntl_map_run_grouped  every read looked up in    <- map_long_reads + read_btllib_minimizers
  *                 the contigs of its own group only    (bin/ntlink_patch_gaps.py:397-442): per gap one read
  *                                                      piece against its two scaffold ends
+ *   ntl_mapres_gap_cuts  orientation, consistency,  <- the rest of map_long_reads (bin/ntlink_patch_gaps.py:443-489),
+ *                 terminal minimizer and the cuts      find_orientation / check_position_consistency (:113-127),
+ *                 of every gap of a grouped result     assign_ctg_cut / assign_read_cut (:291-308),
+ *                                                      assess_accepted_anchor_contigs (:492-517)
  *   ntl_fastx_*   FASTA/FASTQ(.gz) records          <- `gzip -cd -f FILES |` + SeqReader
  *                                                      (ntLink:113-117,222-223)
  *   ntl_tsv_*     indexlr TSV -> arrays             <- the split()s of bin/ntlink_pair.py:197-207,355-378
@@ -327,6 +331,29 @@ int ntl_map_run_grouped(ntl_ctx *ctx, const ntl_sketch *contigs, const uint32_t 
  * way).  NTL_EINVAL for an ordinary result. */
 typedef struct { uint32_t lds_slots; uint64_t groups_in_lds, groups_in_global; } ntl_grouped_info;
 int ntl_mapres_grouped_info(const ntl_mapres *r, ntl_grouped_info *out);
+
+/* The cut points of every gap of a grouped result: what map_long_reads does with the two accepted contigs of a gap
+ * (bin/ntlink_patch_gaps.py:443-489) -- find_orientation and check_position_consistency (:113-127), the terminal minimizer of
+ * assess_accepted_anchor_contigs (:492-517: the source's last hit when the read-based orientation equals the source's sign, else its
+ * first; the target's first when it equals the target's sign, else its last) and assign_read_cut / assign_ctg_cut (:291-308,
+ * situations A-D of :276-288) with the k of the re-mapping (args.k).  The result must come from ntl_map_run_grouped with
+ * ctg_group_off[g] = 2g and read_group_off[g] = g (gap g = read g, its source contig 2g, its target contig 2g + 1) and n_gaps must be
+ * the read sketch's nseq: anything else, or an ordinary result, is NTL_EINVAL.  src_minus[g] / tgt_minus[g]: 1 where the node's sign
+ * in the path is '-'.  The result may still be pending: one kernel is queued behind its own, n_gaps records come back and the call
+ * waits once; no hit and no mapping is downloaded.  A result whose completion failed returns that error.
+ *   status        0: the cuts are valid; otherwise a set of NTL_GAP_* bits and every other field is 0.  The fallback to the old
+ *                 anchors (fallback_old_anchor_cuts, :520-530) and --stringent are the caller's, over this word.
+ *   *_ctg_pos     the terminal hit's ctg_pos        -> pairs[..].source_ctg_cut / target_ctg_cut
+ *   *_read_cut    assign_read_cut of its read_pos   -> pairs[..].source_read_cut / target_read_cut
+ *   *_end_cut     assign_ctg_cut of its ctg_pos     -> the scaffold's three_prime_cut / five_prime_cut
+ *   ori           bit 0 / bit 1: the read-based orientation of source / target is '+' */
+#define NTL_GAP_NOT_TWO 1u           /* len(accepted_anchor_contigs) != 2 (:443) */
+#define NTL_GAP_SRC_MIXED_STRANDS 2u /* find_orientation of the source's hits is None */
+#define NTL_GAP_TGT_MIXED_STRANDS 4u
+#define NTL_GAP_SRC_POSITIONS 8u     /* check_position_consistency of the source's hits is False */
+#define NTL_GAP_TGT_POSITIONS 16u
+typedef struct { uint32_t status, src_ctg_pos, src_read_cut, src_end_cut, tgt_ctg_pos, tgt_read_cut, tgt_end_cut, ori; } ntl_gap_cut;
+int ntl_mapres_gap_cuts(const ntl_mapres *r, const uint8_t *src_minus, const uint8_t *tgt_minus, uint32_t n_gaps, int32_t k, ntl_gap_cut *out);
 
 /* ---- host-side native I/O (no GPU involved) ------------------------------------------------ */
 

@@ -26,7 +26,7 @@ SYMBOLS = [
     "ntl_sketch_from_host", "ntl_overlap_filter",
     "ntl_index_build", "ntl_index_destroy", "ntl_index_size",
     "ntl_map_run", "ntl_mapres_destroy", "ntl_mapres_n_mappings", "ntl_mapres_n_hits", "ntl_mapres_n_pafs",
-    "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_map_run_grouped", "ntl_mapres_grouped_info",
+    "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_map_run_grouped", "ntl_mapres_grouped_info", "ntl_mapres_gap_cuts",
     "ntl_fastx_open", "ntl_fastx_open_range", "ntl_fastx_range", "ntl_fastx_close", "ntl_fastx_error", "ntl_fastx_next", "ntl_fastx_sizes", "ntl_fastx_copy", "ntl_fastx_copy_packed", "ntl_fastx_runs", "ntl_fastx_next_span", "ntl_fastx_parse_span", "ntl_fastx_copy_span", "ntl_fastx_seqs", "ntl_fastx_offsets",
     "ntl_fastx_names", "ntl_fastx_name_offsets", "ntl_write_indexlr", "ntl_write_verbose", "ntl_write_paf",
     "ntl_tsv_open", "ntl_tsv_close", "ntl_tsv_error", "ntl_tsv_next", "ntl_tsv_sizes", "ntl_tsv_copy",
@@ -41,6 +41,9 @@ HIT_DT = np.dtype([("ctg_pos", "<u4"), ("read_pos", "<u4"), ("ctg_strand", "u1")
                    ("pad", "u1", (2,))])
 PAF_DT = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("q_start", "<u4"), ("q_end", "<u4"),
                    ("t_start", "<u4"), ("t_end", "<u4"), ("n_hits", "<u4"), ("strand", "<u4")])
+GAP_CUT_DT = np.dtype([(nm, "<u4") for nm in ("status", "src_ctg_pos", "src_read_cut", "src_end_cut", "tgt_ctg_pos", "tgt_read_cut",
+                                               "tgt_end_cut", "ori")])  # ntl_gap_cut
+NTL_GAP_NOT_TWO, NTL_GAP_SRC_MIXED_STRANDS, NTL_GAP_TGT_MIXED_STRANDS, NTL_GAP_SRC_POSITIONS, NTL_GAP_TGT_POSITIONS = 1, 2, 4, 8, 16
 
 
 class MapParams(C.Structure):
@@ -145,6 +148,7 @@ def load(path=None):
     L.ntl_map_run.argtypes = [vp, vp, vp, u32p, C.POINTER(MapParams), C.POINTER(vp)]
     L.ntl_map_run_grouped.argtypes = [vp, vp, u32p, u32p, vp, u32p, u32p, C.c_uint32, C.POINTER(MapParams), C.POINTER(vp)]
     L.ntl_mapres_grouped_info.argtypes = [vp, C.POINTER(GroupedInfo)]
+    L.ntl_mapres_gap_cuts.argtypes = [vp, vp, vp, C.c_uint32, C.c_int32, vp]
     L.ntl_mapres_destroy.argtypes = [vp]
     L.ntl_mapres_destroy.restype = None
     for nm in ("n_mappings", "n_hits", "n_pafs", "n_index_hits"):
@@ -356,6 +360,18 @@ class MapResult(_Handle):
         info = GroupedInfo()
         self.dev._chk(self.dev.L.ntl_mapres_grouped_info(self.ptr, C.byref(info)))
         return {"lds_slots": int(info.lds_slots), "groups_in_lds": int(info.groups_in_lds), "groups_in_global": int(info.groups_in_global)}
+
+    def gap_cuts(self, src_minus, tgt_minus, k):
+        """Of a result of Device.map_grouped whose group g is contigs 2g, 2g + 1 and read g (ntl_mapres_gap_cuts): one GAP_CUT_DT
+        record per gap -- status (0: valid, else NTL_GAP_* bits and zeros), the terminal minimizers' contig positions, the read cuts,
+        the scaffold end cuts and the read-based orientations -- decided on the device from the hits where they lie.  src_minus /
+        tgt_minus: per gap, true where the node's sign in the path is '-'; k: the k of this mapping.  The result may be pending."""
+        sm = np.ascontiguousarray(src_minus, np.uint8); tm = np.ascontiguousarray(tgt_minus, np.uint8)
+        if sm.ndim != 1 or sm.shape != tm.shape:
+            raise ValueError("src_minus and tgt_minus must have one entry per gap each")
+        out = np.empty(len(sm), GAP_CUT_DT)
+        self.dev._chk(self.dev.L.ntl_mapres_gap_cuts(self.ptr, sm.ctypes.data, tm.ctypes.data, len(sm), int(k), out.ctypes.data))
+        return out
 
     def counts(self):
         self.wait()

@@ -32,6 +32,7 @@
 #include "window_plan.h"
 #include "map_kernels.h"
 #include "group_kernels.h"
+#include "gap_kernels.h"
 #include "pack_kernels.h"
 #include "synth_kernels.h"
 #include "overlap_kernels.h"
@@ -2034,6 +2035,11 @@ struct ntl_mapres {
     bool grouped = false;
     ntl_grouped_info ginfo = {};
     DevBuf ctg_len_own;
+    /* for ntl_mapres_gap_cuts: the scans map_enqueue made for its gather (the first third: u32[n_reads + 1], first mapping of every
+       read), kept instead of freed; the records `maps` and `hits` hold; whether group g is "contigs 2g and 2g + 1, read g" */
+    mutable DevBuf map_off;
+    uint64_t n_reads = 0, rec_cap = 0;
+    bool gap_shaped = false;
 };
 
 /* what map_enqueue queues in place of the index lookup for a grouped result (group_kernels.h) */
@@ -2058,9 +2064,11 @@ static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads,
     const ntl_map_params *params = &R->params;
     int rc;
     hipStream_t ms = c->stream;
-    DevBuf cand, rpos, smaps, spafs, n3, off3, scr, over;
+    DevBuf cand, rpos, smaps, spafs, n3, off3_own, scr, over;
+    DevBuf &off3 = gj ? R->map_off : off3_own; /* a grouped result keeps its offsets (ntl_mapres_gap_cuts) */
     R->dense_made = R->doff_made = false;
     const uint64_t cap = nmx ? nmx : 1;
+    R->n_reads = nreads; R->rec_cap = cap;
     if ((!have_cand && ((rc = cand.alloc(c, cap * sizeof(Cand))) || (rc = rpos.alloc(c, cap * 4)))) ||
         (rc = smaps.alloc(c, cap * sizeof(MapRec))) ||
         (rc = spafs.alloc(c, cap * sizeof(PafRec))) || (rc = n3.alloc(c, 3 * (nreads + 1) * 4)) ||
@@ -2299,6 +2307,8 @@ extern "C" int ntl_map_run_grouped(ntl_ctx *c, const ntl_sketch *ctg, const uint
     const uint64_t n_ctg = ctg->nseq, nreads = reads->nseq;
     ntl_mapres *R = new ntl_mapres();
     R->c = c; R->params = *params; R->grouped = true;
+    R->gap_shaped = ctg->nseq == 2ull * n_groups && reads->nseq == n_groups;
+    for (uint32_t g = 0; R->gap_shaped && g <= n_groups; g++) R->gap_shaped = ctg_group_off[g] == 2u * g && read_group_off[g] == g;
     if (!R->lz.arm(c->pq)) { mapres_free(R); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
     const_cast<ntl_sketch *>(ctg)->refs++;
     R->lz.holds[0] = {ctg, hold_sketch};
@@ -2363,6 +2373,44 @@ extern "C" int ntl_mapres_grouped_info(const ntl_mapres *r, ntl_grouped_info *ou
     if (!r || !out || !r->grouped) return NTL_EINVAL;
     *out = r->ginfo;
     return NTL_OK;
+}
+
+static_assert(sizeof(ntl_gap_cut) == sizeof(GapCut) && sizeof(GapCut) == 32, "ABI record must match the device record");
+static_assert(NTL_GAP_NOT_TWO == GAP_NOT_TWO && NTL_GAP_SRC_MIXED_STRANDS == GAP_SRC_MIXED_STRANDS && NTL_GAP_TGT_MIXED_STRANDS == GAP_TGT_MIXED_STRANDS &&
+              NTL_GAP_SRC_POSITIONS == GAP_SRC_POSITIONS && NTL_GAP_TGT_POSITIONS == GAP_TGT_POSITIONS, "status bits of the ABI and of gap_kernels.h");
+
+/* The kernel goes on MAIN behind the result's own kernels, pending or not; one wait for the records, and the result's completion
+   behind it costs no second one.  Neither the dense hit copy nor any download is involved: the hits are read where the map kernels
+   left them. */
+extern "C" int ntl_mapres_gap_cuts(const ntl_mapres *r, const uint8_t *src_minus, const uint8_t *tgt_minus, uint32_t n_gaps, int32_t k,
+                                   ntl_gap_cut *out)
+{
+    if (!r || k < 0 || (n_gaps && (!src_minus || !tgt_minus || !out))) return NTL_EINVAL;
+    ntl_ctx *c = r->c;
+    (void)hipSetDevice(c->device);
+    if (!r->grouped) return fail(c, NTL_EINVAL, "ntl_mapres_gap_cuts: not a result of ntl_map_run_grouped");
+    if (!r->gap_shaped) return fail(c, NTL_EINVAL, "ntl_mapres_gap_cuts: the groups must be ctg_group_off[g] = 2g, read_group_off[g] = g");
+    if (n_gaps != r->n_reads) return fail(c, NTL_EINVAL, "ntl_mapres_gap_cuts: n_gaps must be the read sketch's number of sequences");
+    if (!r->lz.pending && r->lz.failed) return r->lz.failed;
+    if (!n_gaps) return mapres_finalize(r);
+    DevBuf signs, cuts;
+    int rc;
+    if ((rc = signs.alloc(c, 2ull * n_gaps)) || (rc = cuts.alloc(c, (uint64_t)n_gaps * sizeof(GapCut)))) return rc;
+    HIPCHK(c, hipMemcpyAsync(signs.p, src_minus, n_gaps, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(signs.as<uint8_t>() + n_gaps, tgt_minus, n_gaps, hipMemcpyHostToDevice, c->stream));
+    GapArgs A;
+    A.maps = r->maps.as<MapRec>(); A.hits = r->hits.as<HitRec>(); A.maps_cap = A.hits_cap = r->rec_cap;
+    A.map_off = r->map_off.as<uint32_t>();
+    A.src_minus = signs.as<uint8_t>(); A.tgt_minus = A.src_minus + n_gaps;
+    A.n_gaps = n_gaps; A.k = (uint32_t)k; A.out = cuts.as<GapCut>();
+    {
+        ProfSpan sp(c, "gap_cut");
+        hipLaunchKernelGGL(gap_cut_kernel, dim3((n_gaps + GAP_NT / 64 - 1) / (GAP_NT / 64)), dim3(GAP_NT), 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(out, cuts.p, (uint64_t)n_gaps * sizeof(GapCut), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, main_wait(c));
+    return mapres_finalize(r); /* (its event has passed: no second wait) the error of a result whose completion failed */
 }
 
 /* hit_doff[m] = hits of the mappings before m (the dense numbering of the hits); needs a completed result */

@@ -17,12 +17,23 @@ get_accepted_anchor_contigs.  Here all gaps of a batch are sketched together and
   they do in the reference's dict; the grouped call keeps two contigs apart
 * contig lengths are the records' lengths: the reference's temporary files hold every scaffold N-masked to its full length
 * ``args`` needs ``.k .z .x .sensitive``; ``MinimizerPositions.mx`` is the hash as ``str``
+
+What the loop is for lies behind that call (:443-489): from the two accepted contigs the read's orientation on each scaffold, the
+consistency of the positions, the terminal minimizer of each side and the cuts.  ``gap_cuts`` leaves all of it on the device
+(MapResult.gap_cuts, ntl_mapres_gap_cuts, csrc/gap_kernels.h): per batch sketch, sketch, map_grouped, gap_cuts -- seven integers and a
+status per gap come back, no hit and no sketch.  ``map_long_reads(pairs, scaffolds, args)`` is the drop-in for the reference function:
+it reads the two temporary files of ``args.o`` and writes what :443-489 and fallback_old_anchor_cuts (:520-530) write into ``pairs``
+and ``scaffolds``.
+
+* a gap whose two names come out equal has ONE contig in the reference's dict, so ``len(accepted_anchor_contigs) != 2`` whatever
+  maps: its status is NTL_GAP_NOT_TWO without any mapping (the grouped call, which keeps the two records apart, is overruled)
 """
+import collections
 import re
 
 import numpy as np
 
-from . import anchor, seqio
+from . import anchor, capi, seqio
 from .anchor import ContigRun, Minimizer, MinimizerPositions
 
 _STRAND = ("-", "+")
@@ -129,30 +140,31 @@ def _map_batch(dev, scaffolds, reads, first, k, w, args, with_minimizers, name_o
         yield Gap(recs[0], recs[1], recs[2], accepted[g][0], accepted[g][1])
 
 
-def _map_records(scaffolds, reads, k, w, args, dev, with_minimizers, name_of, batch_bases):
-    """scaffolds, reads: iterators of (id, sequence bytes); batches bounded by bases, a gap never split"""
-    dev = dev or anchor._default_device()
+def _batches(scaffolds, reads, batch_bases):
+    """scaffolds, reads: iterators of (id, sequence bytes); yields (number of the first read record, scaffold records, read records) of
+    every batch: batches bounded by bases, a gap never split"""
     scaffolds, reads = iter(scaffolds), iter(reads)
     first, sb, rb, bases = 0, [], [], 0
-
-    def flush():
-        nonlocal first, sb, rb, bases
-        yield from _map_batch(dev, sb, rb, first, k, w, args, with_minimizers, name_of)
-        first += len(rb)
-        sb, rb, bases = [], [], 0
-
     for read in reads:
         pair = [next(scaffolds, None), next(scaffolds, None)]
         if pair[1] is None:
             raise ValueError("fewer than two scaffold records per read record")
         add = len(read[1]) + len(pair[0][1]) + len(pair[1][1])
         if rb and bases + add > batch_bases:
-            yield from flush()
+            yield first, sb, rb
+            first += len(rb)
+            sb, rb, bases = [], [], 0
         rb.append(read); sb += pair; bases += add
     if next(scaffolds, None) is not None:
         raise ValueError("more than two scaffold records per read record")
     if rb:
-        yield from flush()
+        yield first, sb, rb
+
+
+def _map_records(scaffolds, reads, k, w, args, dev, with_minimizers, name_of, batch_bases):
+    dev = dev or anchor._default_device()
+    for first, sb, rb in _batches(scaffolds, reads, batch_bases):
+        yield from _map_batch(dev, sb, rb, first, k, w, args, with_minimizers, name_of)
 
 
 def map_gap_sequences(scaffolds, reads, k, w, args, dev=None, with_minimizers=False, name_of=default_name_of, batch_bases=BATCH_BASES):
@@ -163,6 +175,116 @@ def map_gap_sequences(scaffolds, reads, k, w, args, dev=None, with_minimizers=Fa
         raise ValueError(f"{len(scaffolds)} scaffold records for {len(reads)} read records: two per read are needed")
     enc = lambda recs: ((i, s.encode() if isinstance(s, str) else s) for i, s in recs)
     return _map_records(enc(scaffolds), enc(reads), k, w, args, dev, with_minimizers, name_of, batch_bases)
+
+
+# ---------------------------------------------------------------- the cuts (bin/ntlink_patch_gaps.py:443-489)
+
+GapCuts = collections.namedtuple("GapCuts", "cuts read_ids scaffold_ids src_minus tgt_minus")
+_READ_HEADER = re.compile(r"^(\S+)__(\S+)__(\S+)$")      # :414
+_SCAFFOLD_HEADER = re.compile(r"^(\S+)_(source|target)$")  # :415
+
+
+def _is_minus(record_id):
+    """the sign :426-433 take from a scaffold record: the character in front of `_source` / `_target`"""
+    sign = _LABEL.sub("", record_id)[-1:]
+    if sign not in ("+", "-"):
+        raise ValueError(f"scaffold record {record_id!r}: + or - is needed in front of _source / _target")
+    return sign == "-"
+
+
+def _cut_batch(dev, scaffolds, reads, k, w, args, name_of):
+    """one device pass over len(reads) gaps: sketch, sketch, map_grouped, gap_cuts; nothing but the cut records comes back"""
+    n = len(reads)
+    src_minus = np.fromiter((_is_minus(scaffolds[2 * g][0]) for g in range(n)), np.uint8, n)
+    tgt_minus = np.fromiter((_is_minus(scaffolds[2 * g + 1][0]) for g in range(n)), np.uint8, n)
+    ctg_len = np.fromiter((len(seq) for _id, seq in scaffolds), np.uint32, 2 * n)
+    read_len = np.fromiter((len(seq) for _id, seq in reads), np.uint32, n)
+    with dev.batch([bytes(seq) for _id, seq in scaffolds]) as sb, dev.batch([bytes(seq) for _id, seq in reads]) as rb, \
+            dev.sketch(sb, k, w) as ssk, dev.sketch(rb, k, w) as rsk, \
+            dev.map_grouped(ssk, ctg_len, 2 * np.arange(n + 1, dtype=np.uint32), rsk, read_len, np.arange(n + 1, dtype=np.uint32),
+                            k=int(args.k), z=int(args.z), x=float(args.x), sensitive=bool(args.sensitive)) as res:
+        cuts = res.gap_cuts(src_minus, tgt_minus, int(args.k))
+    for g in range(n):  # one contig in the reference's dict: never two accepted contigs (see the module's text)
+        if name_of(scaffolds[2 * g][0]) == name_of(scaffolds[2 * g + 1][0]):
+            cuts[g] = (capi.NTL_GAP_NOT_TWO, 0, 0, 0, 0, 0, 0, 0)
+    return cuts, src_minus, tgt_minus
+
+
+def _cut_records(scaffolds, reads, k, w, args, dev, name_of, batch_bases):
+    dev = dev or anchor._default_device()
+    parts, rids, sids = [], [], []
+    for _first, sb, rb in _batches(scaffolds, reads, batch_bases):
+        parts.append(_cut_batch(dev, sb, rb, k, w, args, name_of))
+        rids += [rid for rid, _seq in rb]
+        sids += [sid for sid, _seq in sb]
+    cat = lambda i, dt: np.concatenate([p[i] for p in parts]) if parts else np.empty(0, dt)
+    return GapCuts(cat(0, capi.GAP_CUT_DT), rids, sids, cat(1, np.uint8), cat(2, np.uint8))
+
+
+def gap_cut_sequences(scaffolds, reads, k, w, args, dev=None, name_of=default_name_of, batch_bases=BATCH_BASES):
+    """gap_cuts over records in memory, as map_gap_sequences takes them"""
+    scaffolds, reads = list(scaffolds), list(reads)
+    if len(scaffolds) != 2 * len(reads):
+        raise ValueError(f"{len(scaffolds)} scaffold records for {len(reads)} read records: two per read are needed")
+    enc = lambda recs: ((i, s.encode() if isinstance(s, str) else s) for i, s in recs)
+    return _cut_records(enc(scaffolds), enc(reads), k, w, args, dev, name_of, batch_bases)
+
+
+def gap_cuts(scaffolds_fasta, reads_fasta, k, w, args, dev=None, name_of=default_name_of, batch_bases=BATCH_BASES):
+    """The cuts of every gap of the two temporary files, decided on the device: GapCuts(cuts, read_ids, scaffold_ids, src_minus,
+    tgt_minus) -- cuts: one capi.GAP_CUT_DT record per read record, in file order (status 0: valid; else NTL_GAP_* bits and zeros);
+    src_minus / tgt_minus: 1 where the scaffold record's sign is '-'.  Batches as map_gap_reads makes them."""
+    return _cut_records(_records_of(scaffolds_fasta, batch_bases), _records_of(reads_fasta, batch_bases), k, w, args, dev, name_of,
+                        batch_bases)
+
+
+def _fallback_old_anchor_cuts(pair, scaffolds, source_name, src_minus, target_name, tgt_minus):
+    """fallback_old_anchor_cuts (:520-530)"""
+    pair.old_anchor_used = True
+    if not src_minus:
+        scaffolds[source_name].three_prime_cut = pair.source_ctg_cut
+    else:
+        scaffolds[source_name].five_prime_cut = pair.source_ctg_cut
+    if not tgt_minus:
+        scaffolds[target_name].five_prime_cut = pair.target_ctg_cut
+    else:
+        scaffolds[target_name].three_prime_cut = pair.target_ctg_cut
+
+
+def map_long_reads(pairs, scaffolds, args, dev=None, batch_bases=BATCH_BASES):
+    """The reference's map_long_reads (:412-489): reads ``args.o + ".scaffolds.masked_temp.fa"`` / ``".reads.masked_temp.fa"``, uses
+    ``args.k .w .z .x .sensitive .stringent`` and writes ``pairs[(source, target)].source_ctg_cut / source_read_cut / target_ctg_cut /
+    target_read_cut / old_anchor_used`` and ``scaffolds[name].five_prime_cut / three_prime_cut``.  Gaps are applied in file order: a
+    scaffold can be the source of one gap and the target of another."""
+    got = gap_cuts(args.o + ".scaffolds.masked_temp.fa", args.o + ".reads.masked_temp.fa", int(args.k), int(args.w), args, dev=dev,
+                   batch_bases=batch_bases)
+    for g, cut in enumerate(got.cuts.tolist()):
+        status, src_pos, src_read_cut, src_end_cut, tgt_pos, tgt_read_cut, tgt_end_cut, _ori = cut
+        _, source, target = _READ_HEADER.search(got.read_ids[g]).groups()
+        source_id, label = _SCAFFOLD_HEADER.search(got.scaffold_ids[2 * g]).groups()
+        assert source_id == source and label == "source"
+        target_id, label = _SCAFFOLD_HEADER.search(got.scaffold_ids[2 * g + 1]).groups()
+        assert target_id == target and label == "target"
+        source_name, target_name = source_id.strip("+-"), target_id.strip("+-")
+        src_minus, tgt_minus = bool(got.src_minus[g]), bool(got.tgt_minus[g])
+        pair = pairs[(source, target)]
+        if status:  # not two accepted contigs, mixed strands or inconsistent positions (:443-463)
+            if args.stringent:
+                pair.source_read_cut = None
+                pair.target_read_cut = None
+            else:
+                _fallback_old_anchor_cuts(pair, scaffolds, source_name, src_minus, target_name, tgt_minus)
+            continue
+        pair.source_ctg_cut, pair.source_read_cut = src_pos, src_read_cut
+        if not src_minus:
+            scaffolds[source_name].three_prime_cut = src_end_cut
+        else:
+            scaffolds[source_name].five_prime_cut = src_end_cut
+        pair.target_ctg_cut, pair.target_read_cut = tgt_pos, tgt_read_cut
+        if not tgt_minus:
+            scaffolds[target_name].five_prime_cut = tgt_end_cut
+        else:
+            scaffolds[target_name].three_prime_cut = tgt_end_cut
 
 
 def _records_of(path, batch_bases):

@@ -7,12 +7,19 @@ For G synthetic gaps (two scaffold ends of 300 .. 3000 bases, one read piece acr
             upload, a map and a download each) from the same sketches' arrays, over the first 2000 gaps, scaled to G
   kernel    group_probe_kernel alone (ntl_prof_get "probe") beside the bytes it moves: 16 B per contig record and per read record in,
             12 B per read record out
-Prints one JSON line per G."""
+  cuts      (--cuts) the whole of the reference's map_long_reads over the two temporary files, best of --repeat in one process:
+            gapfill.map_long_reads (the cuts decided by gap_cut_kernel: 32 B per gap come back) beside the way to the same answer before
+            it -- gapfill.map_gap_reads and assess_accepted_anchor_contigs (bin/ntlink_patch_gaps.py:443-517) in Python over its Gap
+            objects; both end states must be equal.  Also gap_cut_kernel alone (ntl_prof_get "gap_cut") and the bytes it reads: per gap
+            two offsets, two signs and, with two mappings, their two records and 12 B per hit.
+Prints one JSON line per G (and one per G for --cuts)."""
 import argparse
 import json
 import sys
 import os
+import tempfile
 import time
+import types
 
 import numpy as np
 
@@ -65,14 +72,114 @@ def per_gap_loop(dev, scaffolds, reads, args, n):
     return time.perf_counter() - t0, two
 
 
+def host_map_long_reads(pairs, scaffolds, args, dev):
+    """map_long_reads before gap_cut_kernel: every hit downloaded and made an object, then :443-517 in Python"""
+    k = args.k
+    gaps = gapfill.map_gap_reads(args.o + ".scaffolds.masked_temp.fa", args.o + ".reads.masked_temp.fa", args.k, args.w, args, dev=dev)
+    for gap in gaps:
+        _, source, target = gap.read.id.split("__")
+        sname, tname = source.strip("+-"), target.strip("+-")
+        pair = pairs[(source, target)]
+        sides = None
+        if len(gap.accepted) == 2:
+            sides = []
+            for name, sign, source_side in ((sname, source[-1], True), (tname, target[-1], False)):
+                hits = gap.accepted[name].hits
+                if all(h.ctg_strand == h.read_strand for h in hits):
+                    ori = "+"
+                elif all(h.ctg_strand != h.read_strand for h in hits):
+                    ori = "-"
+                else:
+                    ori = None
+                consistent = all(a.ctg_pos < b.ctg_pos for a, b in zip(hits, hits[1:])) or all(a.ctg_pos > b.ctg_pos for a, b in zip(hits, hits[1:]))
+                if ori is None or not consistent:
+                    sides = None
+                    break
+                t = hits[-1 if (sign == ori) == source_side else 0]
+                sides.append((t.ctg_pos, t.read_pos + k if ori != sign and sign == "+" else t.read_pos,
+                              t.ctg_pos + k if ori == sign and sign == "-" else t.ctg_pos))
+        if sides is None:
+            if args.stringent:
+                pair.source_read_cut = pair.target_read_cut = None
+            else:
+                gapfill._fallback_old_anchor_cuts(pair, scaffolds, sname, source[-1] == "-", tname, target[-1] == "-")
+            continue
+        pair.source_ctg_cut, pair.source_read_cut, pair.target_ctg_cut, pair.target_read_cut = sides[0][0], sides[0][1], sides[1][0], sides[1][1]
+        setattr(scaffolds[sname], "three_prime_cut" if source[-1] == "+" else "five_prime_cut", sides[0][2])
+        setattr(scaffolds[tname], "five_prime_cut" if target[-1] == "+" else "three_prime_cut", sides[1][2])
+
+
+def cuts_leg(dev, G, repeat):
+    scaffolds, reads = make_gaps(G)
+    rng = np.random.default_rng(G)
+    for g in range(G):  # random signs, every other read against the path
+        s, t = "+-"[int(rng.integers(0, 2))], "+-"[int(rng.integers(0, 2))]
+        scaffolds[2 * g] = (f"s{2 * g}{s}_source", scaffolds[2 * g][1])
+        scaffolds[2 * g + 1] = (f"s{2 * g + 1}{t}_target", scaffolds[2 * g + 1][1])
+        seq = reads[g][1]
+        reads[g] = (f"r{g}__s{2 * g}{s}__s{2 * g + 1}{t}", seq.translate(bytes.maketrans(b"ACGT", b"TGCA"))[::-1] if g & 1 else seq)
+
+    def fresh():
+        pairs = {tuple(rid.split("__")[1:]): types.SimpleNamespace(source_ctg_cut=1, source_read_cut=2, target_ctg_cut=3, target_read_cut=4,
+                                                                   old_anchor_used=False) for rid, _s in reads}
+        scaf = {sid.rsplit("_", 1)[0].strip("+-"): types.SimpleNamespace(five_prime_cut=0, three_prime_cut=len(seq)) for sid, seq in scaffolds}
+        return pairs, scaf
+
+    with tempfile.TemporaryDirectory() as tmp:
+        prefix = os.path.join(tmp, "g")
+        for suffix, recs in ((".scaffolds.masked_temp.fa", scaffolds), (".reads.masked_temp.fa", reads)):
+            with open(prefix + suffix, "wb") as fh:
+                for rid, seq in recs:
+                    fh.write(b">" + rid.encode() + b"\n" + seq + b"\n")
+        args = argparse.Namespace(o=prefix, k=K, w=W, z=1000, x=0.0, sensitive=False, stringent=False)
+        gapfill.map_long_reads(*fresh(), args, dev=dev)  # warm-up
+        t_new, t_old, states = [], [], []
+        for fn, times in ((gapfill.map_long_reads, t_new), (host_map_long_reads, t_old)):
+            for _ in range(repeat):
+                pairs, scaf = fresh()
+                t0 = time.perf_counter()
+                fn(pairs, scaf, args, dev)
+                times.append(time.perf_counter() - t0)
+            states.append(([vars(p) for p in pairs.values()], {n: vars(s) for n, s in scaf.items()}))
+        assert states[0] == states[1], "the two ways leave different cuts"
+    # the kernel alone: one stream, events round it
+    dev.set_pipeline(False)
+    dev.prof_enable(True)
+    dev.prof_reset()
+    minus = np.zeros(G, np.uint8)
+    with dev.batch([s for _i, s in scaffolds]) as sb, dev.batch([s for _i, s in reads]) as rb, dev.sketch(sb, K, W) as ssk, dev.sketch(rb, K, W) as rsk:
+        clen = np.array([len(s) for _i, s in scaffolds], np.uint32); rlen = np.array([len(s) for _i, s in reads], np.uint32)
+        with dev.map_grouped(ssk, clen, 2 * np.arange(G + 1, dtype=np.uint32), rsk, rlen, np.arange(G + 1, dtype=np.uint32), k=K) as res:
+            for _ in range(repeat):
+                cuts = res.gap_cuts(minus, minus, K)
+            maps = res.download()["maps"]
+    ms, launches = dev.prof_get("gap_cut")
+    dev.prof_enable(False)
+    dev.set_pipeline(True)
+    two = np.flatnonzero(np.bincount(maps["read"], minlength=G) == 2)
+    read_bytes = 10 * G + int(np.isin(maps["read"], two).sum()) * 24 + 12 * int(maps["n_hits"][np.isin(maps["read"], two)].sum())
+    kernel_ms = ms / max(1, launches)
+    new_cuts = sum(not p["old_anchor_used"] for p in states[0][0])
+    print(json.dumps({"leg": "cuts", "gaps": G, "map_long_reads_s": min(t_new), "map_long_reads_s_all": t_new, "host_assess_s": min(t_old),
+                      "host_assess_s_all": t_old, "ratio": min(t_old) / min(t_new), "new_cuts": new_cuts, "valid_status": int((cuts["status"] == 0).sum()),
+                      "gap_cut_kernel_ms": kernel_ms, "gap_cut_read_bytes": read_bytes, "gap_cut_GBps": read_bytes / kernel_ms / 1e6 if kernel_ms else None,
+                      "device": dev.name}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gaps", type=int, nargs="+", default=[2000, 20000])
     ap.add_argument("--per-gap", type=int, default=2000, help="gaps the per-gap loop runs over (scaled to G)")
     ap.add_argument("--repeat", type=int, default=3)
+    ap.add_argument("--cuts", action="store_true", help="the cuts leg alone: gapfill.map_long_reads beside map_gap_reads + the assess in Python")
     a = ap.parse_args()
     args = argparse.Namespace(k=K, z=1000, x=0.0, sensitive=False)
     dev = capi.Device(0)
+    if a.cuts:
+        for G in a.gaps:
+            cuts_leg(dev, G, a.repeat)
+        dev.close()
+        return
     for G in a.gaps:
         scaffolds, reads = make_gaps(G)
         list(gapfill.map_gap_sequences(scaffolds[:200], reads[:100], K, W, args, dev=dev))  # warm-up: code objects, pools
