@@ -355,6 +355,44 @@ int ntl_mapres_grouped_info(const ntl_mapres *r, ntl_grouped_info *out);
 typedef struct { uint32_t status, src_ctg_pos, src_read_cut, src_end_cut, tgt_ctg_pos, tgt_read_cut, tgt_end_cut, ori; } ntl_gap_cut;
 int ntl_mapres_gap_cuts(const ntl_mapres *r, const uint8_t *src_minus, const uint8_t *tgt_minus, uint32_t n_gaps, int32_t k, ntl_gap_cut *out);
 
+/* Which read supports which gap, and the cuts it would give: tally_contig_mapping_info (bin/ntlink_patch_gaps.py:149-175),
+ * is_valid_supporting_read with calculate_est_gap_size (:208-246) and find_masking_cut_points (:311-342) over one block of
+ * <prefix>.verbose_mapping.tsv as ntl_vmap_copy delivers it: read r has the mappings maps[map_off[r] .. map_off[r + 1]) in file order
+ * (map_off[0] = 0, non-decreasing, map_off[n_reads] = n_maps), mapping m column 3 as anchors[m], the hits hits[hit_off .. hit_off +
+ * n_hits) and its contig's number in the caller's name table (0xFFFFFFFF: not in it, matches no pair; fewer than 2^31 - 1 contigs);
+ * ctg_len[n_ctg] the contigs' lengths (sequences[..].length), large_k = args.large_k.
+ *
+ * The pairs of the path file come as an open-addressing table made by ntl_gap_pair_table: keys[i] = (source node << 32 | target
+ * node), node = contig number << 1 | (1 where the sign is '-'), is pair i.  n_slots is a power of two and at least twice the pairs
+ * (a table more than half full, or another slot count: NTL_EINVAL); a probe sequence that does not end within the table fails the
+ * call with NTL_EINTERNAL instead of hanging.
+ *
+ * A mapping is valid iff find_orientation gives '+' or '-' and check_position_consistency holds (:113-127); the read's `length` is the
+ * read_pos of the last hit of its last valid mapping (:163).  Every combination i < j of a read's valid mappings, in
+ * itertools.combinations order, is looked up as (i, j) and then as reverse_complement_pair(i, j), each node with the mapping's own
+ * orientation: every pair found is one candidate record, in the order read, combination, direct before reverse complement.
+ *   pair, read    the pair's number; the read's number in the block
+ *   anchors       int(anchors) of the pair's two contigs, summed (numpy.mean of the two orders as their sum does, :257)
+ *   flags         NTL_GAPSEL_VALID: abs(gap_est) <= length (:243); NTL_GAPSEL_NEGATIVE: a < 0 or b < 0, where the reference asserts
+ *                 (:222-223); NTL_GAPSEL_VIA_REVCOMP: found as the reverse complement
+ *   *_cut         what find_masking_cut_points would write into the pair for this read (assign_ctg_cut / assign_read_cut with large_k)
+ * Two valid mappings of one read on the same contig -- a dict overwrite in the reference, never written by `pair` -- fail the call
+ * with NTL_EINVAL.  One host wait for the count, one for the records; no hit and no mapping comes back. */
+#define NTL_GAPSEL_VALID 1u
+#define NTL_GAPSEL_NEGATIVE 2u
+#define NTL_GAPSEL_VIA_REVCOMP 4u
+typedef struct { uint32_t pair, read, anchors, flags, source_ctg_cut, source_read_cut, target_ctg_cut, target_read_cut; } ntl_gap_cand;
+typedef struct ntl_gap_cands ntl_gap_cands;
+/* Host only: slot_keys[n_slots] / slot_vals[n_slots] from keys[n_pairs] (distinct, none all ones); NTL_EINVAL unless n_slots is a
+ * power of two >= max(2, 2 n_pairs). */
+int ntl_gap_pair_table(const uint64_t *keys, uint64_t n_pairs, uint64_t *slot_keys, uint32_t *slot_vals, uint64_t n_slots);
+int ntl_gap_select(ntl_ctx *ctx, const uint32_t *map_off, uint32_t n_reads, const ntl_mapping *maps, const uint32_t *anchors,
+                   uint64_t n_maps, const ntl_hit *hits, uint64_t n_hits, const uint32_t *ctg_len, uint32_t n_ctg, int32_t large_k,
+                   const uint64_t *slot_keys, const uint32_t *slot_vals, uint64_t n_slots, ntl_gap_cands **out);
+uint64_t ntl_gap_cands_count(const ntl_gap_cands *s);
+int ntl_gap_cands_copy(const ntl_gap_cands *s, ntl_gap_cand *out);
+void ntl_gap_cands_destroy(ntl_gap_cands *s);
+
 /* ---- host-side native I/O (no GPU involved) ------------------------------------------------ */
 
 /* FASTA/FASTQ(.gz) reader = `gzip -cd -f FILE | SeqReader` of the reference's pipe
@@ -429,6 +467,28 @@ int ntl_tsv_next(ntl_tsv *r, uint64_t max_bytes, uint64_t *nrec);
 void ntl_tsv_sizes(const ntl_tsv *r, uint64_t *nrec, uint64_t *nmx, uint64_t *name_bytes);
 int ntl_tsv_copy(const ntl_tsv *r, char *names, uint64_t *name_off, uint32_t *lengths, uint64_t *mx_off,
                  uint64_t *hash, uint32_t *pos, uint8_t *strand);
+
+/* Reader of <prefix>.verbose_mapping.tsv for the gap filler: the loop of read_verbose_mappings with the split()s of
+ * tally_contig_mapping_info and ntlink_utils.parse_minimizers (bin/ntlink_patch_gaps.py:178-198,153-154) -- lines
+ * `read\tcontig\tanchors\tctgpos:ctgstrand_readpos:readstrand ...`, several threads over blocks of whole READS: consecutive lines with
+ * the same first column stay in one block (one read, as in the reference; the same id again further on is another read).
+ * ntl_vmap_open takes the contig name table (name i = ctg_names[ctg_name_off[i] .. ctg_name_off[i + 1]), copied).  ntl_vmap_next reads
+ * about max_bytes of text (0 = all of it; more where one read's lines need it) and counts; *n_reads == 0 at the end.  ntl_vmap_copy
+ * fills caller-allocated arrays: read r has the id names[name_off[r] .. name_off[r + 1]) and the lines map_off[r] .. map_off[r + 1]
+ * (name_off / map_off: n_reads + 1 entries); line m is maps[m] -- read = r, ctg = the contig's number in the table or 0xFFFFFFFF for a
+ * name that is not in it, n_hits = its tokens, hit_off dense -- with column 3 as written in anchors[m] (the reference scores with
+ * int(anchors), not with the token count) and the tokens in hits[].  What ntl_gap_select takes.
+ * A line that is not four tab-separated fields, a token that is not int:+-_int:+-, column 3 not a number, or a number above
+ * 2^32 - 1 fails ntl_vmap_next with NTL_EINVAL and "line N: ..." (N counts from 1 over the whole file) in ntl_vmap_error: never a
+ * partial block.  The checkpoint and liftover readers are not this one. */
+typedef struct ntl_vmap ntl_vmap;
+int ntl_vmap_open(const char *path, const char *ctg_names, const uint64_t *ctg_name_off, uint64_t n_ctg, ntl_vmap **out);
+void ntl_vmap_close(ntl_vmap *r);
+const char *ntl_vmap_error(const ntl_vmap *r);
+int ntl_vmap_next(ntl_vmap *r, uint64_t max_bytes, uint64_t *n_reads);
+void ntl_vmap_sizes(const ntl_vmap *r, uint64_t *n_reads, uint64_t *n_maps, uint64_t *n_hits, uint64_t *name_bytes);
+int ntl_vmap_copy(const ntl_vmap *r, char *names, uint64_t *name_off, uint32_t *map_off, ntl_mapping *maps, uint32_t *anchors,
+                  ntl_hit *hits);
 
 /* ---- the text of the mapping outputs, made on the device ------------------------------------
  * Replaces the formatting loops of bin/ntlink_pair.py:308-313,382-388 (<prefix>.verbose_mapping.tsv) and

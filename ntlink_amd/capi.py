@@ -30,6 +30,8 @@ SYMBOLS = [
     "ntl_fastx_open", "ntl_fastx_open_range", "ntl_fastx_range", "ntl_fastx_close", "ntl_fastx_error", "ntl_fastx_next", "ntl_fastx_sizes", "ntl_fastx_copy", "ntl_fastx_copy_packed", "ntl_fastx_runs", "ntl_fastx_next_span", "ntl_fastx_parse_span", "ntl_fastx_copy_span", "ntl_fastx_seqs", "ntl_fastx_offsets",
     "ntl_fastx_names", "ntl_fastx_name_offsets", "ntl_write_indexlr", "ntl_write_verbose", "ntl_write_paf",
     "ntl_tsv_open", "ntl_tsv_close", "ntl_tsv_error", "ntl_tsv_next", "ntl_tsv_sizes", "ntl_tsv_copy",
+    "ntl_vmap_open", "ntl_vmap_close", "ntl_vmap_error", "ntl_vmap_next", "ntl_vmap_sizes", "ntl_vmap_copy",
+    "ntl_gap_pair_table", "ntl_gap_select", "ntl_gap_cands_count", "ntl_gap_cands_copy", "ntl_gap_cands_destroy",
     "ntl_tally_create", "ntl_tally_destroy", "ntl_tally_add", "ntl_tally_npairs", "ntl_tally_ngaps", "ntl_tally_export", "ntl_tally_merge",
     "ntl_liftover",
     "ntl_names_create", "ntl_names_destroy", "ntl_mapres_format", "ntl_text_sizes", "ntl_text_download", "ntl_text_destroy", "ntl_write_blob",
@@ -44,6 +46,10 @@ PAF_DT = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("q_start", "<u4"), ("q_end"
 GAP_CUT_DT = np.dtype([(nm, "<u4") for nm in ("status", "src_ctg_pos", "src_read_cut", "src_end_cut", "tgt_ctg_pos", "tgt_read_cut",
                                                "tgt_end_cut", "ori")])  # ntl_gap_cut
 NTL_GAP_NOT_TWO, NTL_GAP_SRC_MIXED_STRANDS, NTL_GAP_TGT_MIXED_STRANDS, NTL_GAP_SRC_POSITIONS, NTL_GAP_TGT_POSITIONS = 1, 2, 4, 8, 16
+GAP_CAND_DT = np.dtype([(nm, "<u4") for nm in ("pair", "read", "anchors", "flags", "source_ctg_cut", "source_read_cut", "target_ctg_cut",
+                                                "target_read_cut")])  # ntl_gap_cand
+NTL_GAPSEL_VALID, NTL_GAPSEL_NEGATIVE, NTL_GAPSEL_VIA_REVCOMP = 1, 2, 4
+NO_CTG = 0xFFFFFFFF  # ntl_mapping.ctg of a name that is not in the reader's table
 
 
 class MapParams(C.Structure):
@@ -189,6 +195,22 @@ def load(path=None):
     L.ntl_tsv_sizes.argtypes = [vp, u64p, u64p, u64p]
     L.ntl_tsv_sizes.restype = None
     L.ntl_tsv_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.ntl_vmap_open.argtypes = [C.c_char_p, vp, u64p, C.c_uint64, C.POINTER(vp)]
+    L.ntl_vmap_close.argtypes = [vp]
+    L.ntl_vmap_close.restype = None
+    L.ntl_vmap_error.argtypes = [vp]
+    L.ntl_vmap_error.restype = C.c_char_p
+    L.ntl_vmap_next.argtypes = [vp, C.c_uint64, u64p]
+    L.ntl_vmap_sizes.argtypes = [vp, u64p, u64p, u64p, u64p]
+    L.ntl_vmap_sizes.restype = None
+    L.ntl_vmap_copy.argtypes = [vp, vp, vp, vp, vp, vp, vp]
+    L.ntl_gap_pair_table.argtypes = [vp, C.c_uint64, vp, vp, C.c_uint64]
+    L.ntl_gap_select.argtypes = [vp, vp, C.c_uint32, vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint32, C.c_int32, vp, vp, C.c_uint64, C.POINTER(vp)]
+    L.ntl_gap_cands_count.argtypes = [vp]
+    L.ntl_gap_cands_count.restype = C.c_uint64
+    L.ntl_gap_cands_copy.argtypes = [vp, vp]
+    L.ntl_gap_cands_destroy.argtypes = [vp]
+    L.ntl_gap_cands_destroy.restype = None
     L.ntl_tally_create.argtypes = [vp, u64p, u32p, C.c_uint64, C.c_int, C.c_int, C.POINTER(vp)]
     L.ntl_tally_destroy.argtypes = [vp]
     L.ntl_tally_destroy.restype = None
@@ -644,6 +666,26 @@ class Device:
                                             C.byref(p)))
         return Sketch(self, p)
 
+    def gap_select(self, block, ctg_len, large_k, table):
+        """The candidates of one block of verbose mappings (ntl_gap_select, csrc/gap_select_kernels.h): `block` as formats.read_verbose
+        yields it (.map_off .maps .anchors .hits), ctg_len[n_ctg] of the reader's contig table, `table` = pair_table(keys).  ->
+        GAP_CAND_DT records in the order read, combination, direct before reverse complement."""
+        mo = np.ascontiguousarray(block.map_off, np.uint32); maps = np.ascontiguousarray(block.maps, MAPPING_DT)
+        anc = np.ascontiguousarray(block.anchors, np.uint32); hits = np.ascontiguousarray(block.hits, HIT_DT)
+        cl = np.ascontiguousarray(ctg_len, np.uint32)
+        keys, vals = np.ascontiguousarray(table[0], np.uint64), np.ascontiguousarray(table[1], np.uint32)
+        if len(anc) != len(maps) or len(vals) != len(keys) or len(mo) < 1:
+            raise ValueError("one anchors entry per mapping, one value per slot, n_reads + 1 offsets")
+        p = C.c_void_p()
+        self._chk(self.L.ntl_gap_select(self.ptr, mo.ctypes.data, len(mo) - 1, maps.ctypes.data, anc.ctypes.data, len(maps), hits.ctypes.data, len(hits),
+                                        cl.ctypes.data, len(cl), int(large_k), keys.ctypes.data, vals.ctypes.data, len(keys), C.byref(p)))
+        try:
+            out = np.empty(int(self.L.ntl_gap_cands_count(p)), GAP_CAND_DT)
+            self._chk(self.L.ntl_gap_cands_copy(p, out.ctypes.data))
+        finally:
+            self.L.ntl_gap_cands_destroy(p)
+        return out
+
     def names(self, names, lengths):
         """Device copy of a name table (seqio.Names or a list of str / bytes) with the sequences' lengths."""
         from .seqio import Names
@@ -691,3 +733,22 @@ class Device:
         self._chk(self.L.ntl_map_run_grouped(self.ptr, contig_sketch.ptr, _ptr(cl, C.c_uint32), _ptr(co, C.c_uint32), read_sketch.ptr,
                                              _ptr(rl, C.c_uint32), _ptr(ro, C.c_uint32), len(co) - 1, C.byref(P), C.byref(p)))
         return MapResult(self, p)
+
+
+def pair_key(src_ctg, src_minus, tgt_ctg, tgt_minus):
+    """the 64-bit key of a path pair in ntl_gap_select's table: source node << 32 | target node, node = contig << 1 | minus"""
+    return ((int(src_ctg) << 1 | int(bool(src_minus))) << 32) | (int(tgt_ctg) << 1 | int(bool(tgt_minus)))
+
+
+def pair_table(keys, n_slots=None, lib_path=None):
+    """(slot_keys u64, slot_vals u32) of ntl_gap_pair_table: keys[i] is pair i; by default the smallest power of two of slots that
+    leaves the table at most half full."""
+    keys = np.ascontiguousarray(keys, np.uint64)
+    if n_slots is None:
+        n_slots = 2
+        while n_slots < 2 * len(keys):
+            n_slots *= 2
+    sk, sv = np.empty(n_slots, np.uint64), np.empty(n_slots, np.uint32)
+    if load(lib_path).ntl_gap_pair_table(keys.ctypes.data, len(keys), sk.ctypes.data, sv.ctypes.data, n_slots) != 0:
+        raise ValueError("ntl_gap_pair_table: distinct keys and a power of two of at least twice as many slots are needed")
+    return sk, sv

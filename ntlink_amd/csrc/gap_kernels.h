@@ -40,11 +40,9 @@ struct GapArgs {
     GapCut *out;
 };
 
-/* One mapping on one wavefront.  Returns the mixed-strands bit (1) and the positions bit (2); plus: the read-based orientation is '+';
- * lane 0 alone holds the terminal hit of a mapping without a flag: `last_if_same` says which end it is when the read-based orientation
- * equals the contig's sign (the source: the last hit, the target: the first). */
-__device__ __forceinline__ uint32_t gap_assess(const HitRec *hits, uint32_t n, uint32_t lane, bool ctg_minus, bool last_if_same, bool &plus,
-                                               HitRec &terminal)
+/* The four all() of find_orientation and check_position_consistency over one mapping's hits on one wavefront, the same in every lane
+ * (gap_cut_kernel, and gap_select_assess_kernel of gap_select_kernels.h). */
+__device__ __forceinline__ void gap_ballots(const HitRec *hits, uint32_t n, uint32_t lane, bool &all_same, bool &all_diff, bool &all_inc, bool &all_dec)
 {
     bool same = true, diff = true, inc = true, dec = true;
     for (uint32_t j = lane; j < n; j += 64u) {
@@ -57,8 +55,18 @@ __device__ __forceinline__ uint32_t gap_assess(const HitRec *hits, uint32_t n, u
             dec &= h.ctg_pos > next;
         }
     }
-    const bool all_same = __ballot(!same) == 0ull, all_diff = __ballot(!diff) == 0ull;
-    const bool all_inc = __ballot(!inc) == 0ull, all_dec = __ballot(!dec) == 0ull;
+    all_same = __ballot(!same) == 0ull; all_diff = __ballot(!diff) == 0ull;
+    all_inc = __ballot(!inc) == 0ull; all_dec = __ballot(!dec) == 0ull;
+}
+
+/* One mapping on one wavefront.  Returns the mixed-strands bit (1) and the positions bit (2); plus: the read-based orientation is '+';
+ * lane 0 alone holds the terminal hit of a mapping without a flag: `last_if_same` says which end it is when the read-based orientation
+ * equals the contig's sign (the source: the last hit, the target: the first). */
+__device__ __forceinline__ uint32_t gap_assess(const HitRec *hits, uint32_t n, uint32_t lane, bool ctg_minus, bool last_if_same, bool &plus,
+                                               HitRec &terminal)
+{
+    bool all_same, all_diff, all_inc, all_dec;
+    gap_ballots(hits, n, lane, all_same, all_diff, all_inc, all_dec);
     plus = all_same; /* find_orientation asks for '+' first */
     const uint32_t flags = (all_same || all_diff ? 0u : 1u) | (all_inc || all_dec ? 0u : 2u);
     if (lane == 0 && flags == 0) {

@@ -33,6 +33,7 @@
 #include "map_kernels.h"
 #include "group_kernels.h"
 #include "gap_kernels.h"
+#include "gap_select_kernels.h"
 #include "pack_kernels.h"
 #include "synth_kernels.h"
 #include "overlap_kernels.h"
@@ -2412,6 +2413,111 @@ extern "C" int ntl_mapres_gap_cuts(const ntl_mapres *r, const uint8_t *src_minus
     HIPCHK(c, main_wait(c));
     return mapres_finalize(r); /* (its event has passed: no second wait) the error of a result whose completion failed */
 }
+
+/* ------------------------------------------------------------------ gap filling: the read of every gap ---- */
+
+struct ntl_gap_cands { std::vector<GapCand> rec; };
+
+static_assert(sizeof(ntl_gap_cand) == sizeof(GapCand) && sizeof(GapCand) == 32, "ABI record must match the device record");
+static_assert(NTL_GAPSEL_VALID == GSEL_VALID && NTL_GAPSEL_NEGATIVE == GSEL_NEGATIVE && NTL_GAPSEL_VIA_REVCOMP == GSEL_VIA_REVCOMP,
+              "flag bits of the ABI and of gap_select_kernels.h");
+static_assert(sizeof(ntl_mapping) == sizeof(MapRec) && sizeof(ntl_hit) == sizeof(HitRec), "the reader's records are the device's");
+
+extern "C" int ntl_gap_pair_table(const uint64_t *keys, uint64_t n_pairs, uint64_t *slot_keys, uint32_t *slot_vals, uint64_t n_slots)
+{
+    if ((n_pairs && !keys) || !slot_keys || !slot_vals || n_pairs >= 0xFFFFFFFFull) return NTL_EINVAL;
+    if (n_slots < 2 || (n_slots & (n_slots - 1)) || n_slots > (1ull << 32) || n_slots / 2 < n_pairs) return NTL_EINVAL;
+    for (uint64_t s = 0; s < n_slots; s++) { slot_keys[s] = GSEL_EMPTY; slot_vals[s] = 0; }
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        if (keys[i] == GSEL_EMPTY) return NTL_EINVAL;
+        uint64_t s = gsel_slot(keys[i], n_slots);
+        while (slot_keys[s] != GSEL_EMPTY) { /* at most half full: an empty slot is met */
+            if (slot_keys[s] == keys[i]) return NTL_EINVAL;
+            s = (s + 1) & (n_slots - 1);
+        }
+        slot_keys[s] = keys[i]; slot_vals[s] = (uint32_t)i;
+    }
+    return NTL_OK;
+}
+
+/* Three kernels and a scan on MAIN (gap_select_kernels.h): assess, count, device_scan -- the one wait that sizes the records --
+   fill, and a second wait for the records and the error word. */
+extern "C" int ntl_gap_select(ntl_ctx *c, const uint32_t *map_off, uint32_t n_reads, const ntl_mapping *maps, const uint32_t *anchors,
+                              uint64_t n_maps, const ntl_hit *hits, uint64_t n_hits, const uint32_t *ctg_len, uint32_t n_ctg, int32_t large_k,
+                              const uint64_t *slot_keys, const uint32_t *slot_vals, uint64_t n_slots, ntl_gap_cands **out)
+{
+    if (!c || !out || !map_off || !slot_keys || !slot_vals || large_k < 0 || (n_maps && (!maps || !anchors)) || (n_hits && !hits) ||
+        (n_ctg && !ctg_len))
+        return NTL_EINVAL;
+    *out = nullptr;
+    (void)hipSetDevice(c->device);
+    if (n_ctg >= 0x7FFFFFFFu) return fail(c, NTL_EINVAL, "ntl_gap_select: fewer than 2^31 - 1 contigs");
+    if (n_reads == 0xFFFFFFFFu || n_maps >= 0xFFFFFF00ull) return fail(c, NTL_EINVAL, "ntl_gap_select: too many reads or mappings in one block");
+    if (map_off[0] != 0 || map_off[n_reads] != n_maps) return fail(c, NTL_EINVAL, "ntl_gap_select: map_off must start at 0 and end at n_maps");
+    for (uint32_t r = 0; r < n_reads; r++)
+        if (map_off[r + 1] < map_off[r]) return fail(c, NTL_EINVAL, "ntl_gap_select: map_off must be non-decreasing");
+    if (n_slots < 2 || (n_slots & (n_slots - 1)) || n_slots > (1ull << 32)) return fail(c, NTL_EINVAL, "ntl_gap_select: the pair table's slot count must be a power of two");
+    uint64_t filled = 0;
+    for (uint64_t s = 0; s < n_slots; s++) filled += slot_keys[s] != GSEL_EMPTY;
+    if (filled > n_slots / 2) return fail(c, NTL_EINVAL, "ntl_gap_select: the pair table is more than half full");
+    std::unique_ptr<ntl_gap_cands> o(new ntl_gap_cands());
+    if (!n_reads || !n_maps || !filled) { *out = o.release(); return NTL_OK; }
+    DevBuf d_off, d_maps, d_anc, d_hits, d_len, d_keys, d_vals, d_state, d_length, d_cnt, d_err, d_out;
+    int rc;
+    if ((rc = d_off.alloc(c, ((uint64_t)n_reads + 1) * 4)) || (rc = d_maps.alloc(c, n_maps * sizeof(MapRec))) || (rc = d_anc.alloc(c, n_maps * 4)) ||
+        (rc = d_hits.alloc(c, (n_hits + 1) * sizeof(HitRec))) || (rc = d_len.alloc(c, ((uint64_t)n_ctg + 1) * 4)) || (rc = d_keys.alloc(c, n_slots * 8)) ||
+        (rc = d_vals.alloc(c, n_slots * 4)) || (rc = d_state.alloc(c, n_maps)) || (rc = d_length.alloc(c, (uint64_t)n_reads * 4)) ||
+        (rc = d_cnt.alloc(c, ((uint64_t)n_reads + 1) * 4)) || (rc = d_err.alloc(c, 4)))
+        return rc;
+    GselArgs A;
+    A.map_off = d_off.as<uint32_t>(); A.maps = d_maps.as<MapRec>(); A.anchors = d_anc.as<uint32_t>(); A.hits = d_hits.as<HitRec>();
+    A.n_maps = n_maps; A.n_hits = n_hits; A.n_reads = n_reads; A.n_ctg = n_ctg; A.k = (uint32_t)large_k;
+    A.ctg_len = d_len.as<uint32_t>(); A.pair_keys = d_keys.as<unsigned long long>(); A.pair_vals = d_vals.as<uint32_t>(); A.n_slots = n_slots;
+    A.mstate = d_state.as<uint8_t>(); A.length = d_length.as<uint32_t>(); A.cnt = d_cnt.as<uint32_t>(); A.err = d_err.as<uint32_t>();
+    A.out = nullptr; A.out_cap = 0;
+    HIPCHK(c, hipMemcpyAsync(d_off.p, map_off, ((uint64_t)n_reads + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_maps.p, maps, n_maps * sizeof(MapRec), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_anc.p, anchors, n_maps * 4, hipMemcpyHostToDevice, c->stream));
+    if (n_hits) HIPCHK(c, hipMemcpyAsync(d_hits.p, hits, n_hits * sizeof(HitRec), hipMemcpyHostToDevice, c->stream));
+    if (n_ctg) HIPCHK(c, hipMemcpyAsync(d_len.p, ctg_len, (uint64_t)n_ctg * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_keys.p, slot_keys, n_slots * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_vals.p, slot_vals, n_slots * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_err.p, 0, 4, c->stream));
+    const dim3 grid((n_reads + GSEL_NT / 64 - 1) / (GSEL_NT / 64)), block(GSEL_NT);
+    uint32_t total = 0, err = 0;
+    {
+        ProfSpan sp(c, "gap_select");
+        hipLaunchKernelGGL(gap_select_assess_kernel, grid, block, 0, c->stream, A);
+        hipLaunchKernelGGL(gap_select_count_kernel, grid, block, 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = device_scan(c, A.cnt, A.cnt, n_reads, &total))) return rc; /* waits: the caller's arrays are free again */
+        if (total) {
+            if ((rc = d_out.alloc(c, (uint64_t)total * sizeof(GapCand)))) return rc;
+            A.out = d_out.as<GapCand>(); A.out_cap = total;
+            hipLaunchKernelGGL(gap_select_fill_kernel, grid, block, 0, c->stream, A);
+            HIPCHK(c, hipGetLastError());
+        }
+    }
+    o->rec.resize(total);
+    if (total) HIPCHK(c, hipMemcpyAsync(o->rec.data(), d_out.p, (uint64_t)total * sizeof(GapCand), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&err, d_err.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, main_wait(c));
+    if (err & GSEL_ERR_PROBE) return fail(c, NTL_EINTERNAL, "ntl_gap_select: a probe sequence did not end within the pair table (gap_select_kernels.h)");
+    if (err & GSEL_ERR_SAME_CTG) return fail(c, NTL_EINVAL, "ntl_gap_select: two valid mappings of one read name the same contig");
+    *out = o.release();
+    return NTL_OK;
+}
+
+extern "C" uint64_t ntl_gap_cands_count(const ntl_gap_cands *s) { return s ? s->rec.size() : 0; }
+
+extern "C" int ntl_gap_cands_copy(const ntl_gap_cands *s, ntl_gap_cand *out)
+{
+    if (!s || (!out && !s->rec.empty())) return NTL_EINVAL;
+    if (!s->rec.empty()) memcpy(out, s->rec.data(), s->rec.size() * sizeof(GapCand));
+    return NTL_OK;
+}
+
+extern "C" void ntl_gap_cands_destroy(ntl_gap_cands *s) { delete s; }
 
 /* hit_doff[m] = hits of the mappings before m (the dense numbering of the hits); needs a completed result */
 static int mapres_dense_offsets(const ntl_mapres *r)

@@ -13,6 +13,8 @@
  *   ntl_write_indexlr  the TSV `indexlr --long --pos --strand [--len]` prints (ntLink:199,223).
  *   ntl_write_verbose  <prefix>.verbose_mapping.tsv lines (bin/ntlink_pair.py:308-313,382-388).
  *   ntl_write_paf      <prefix>.paf lines (bin/ntlink_paf_output.py:131-135).
+ *   ntl_vmap_*         <prefix>.verbose_mapping.tsv back into mappings and hits, read by read, for the gap filler
+ *                      (read_verbose_mappings, bin/ntlink_patch_gaps.py:178-198).
  *
  * Formatting is split over threads by record ranges; every thread fills its own buffer and the
  * buffers are written in order.
@@ -37,6 +39,7 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "../../include/ntlink_amd.h"
@@ -580,6 +583,7 @@ static const LibDeflate &libdeflate() { static LibDeflate L; return L; }
 struct BufCache {
     std::mutex mu;
     std::vector<std::pair<char *, size_t>> free_list;
+    ~BufCache() { for (auto &e : free_list) free(e.first); }
     char *take(size_t want, size_t *cap)
     {
         {
@@ -2136,6 +2140,337 @@ extern "C" int ntl_tsv_copy(const ntl_tsv *r, char *names, uint64_t *name_off, u
         const TsvRange &g = r->ranges[t];
         TsvWrite w{names, name_off, lengths, mx_off, hash, pos, strand, r0[t], m0[t], n0[t]};
         tsv_parse(g.b, g.e, r->with_len, r->pos_only, w);
+    });
+    return NTL_OK;
+}
+
+/* ------------------------------------------------------------------ verbose-mapping reader ---- */
+
+/*
+ * <prefix>.verbose_mapping.tsv for the gap filler (read_verbose_mappings, bin/ntlink_patch_gaps.py:178-198): every line is
+ * strip()ped and split on tabs into read, contig, anchors and the tokens `ctgpos:ctgstrand_readpos:readstrand` separated by single
+ * spaces (tally_contig_mapping_info :153-154, ntlink_utils.parse_minimizers); consecutive lines with one read id are one read.  The
+ * scheme is ntl_tsv's -- blocks of the input cut into ranges, counted, then written into the caller's arrays by the worker pool --
+ * with cuts only where the read id changes, so that a read never straddles two ranges or two blocks.
+ */
+struct VmapRange {
+    const char *b = nullptr, *e = nullptr;
+    uint64_t n_reads = 0, n_maps = 0, n_hits = 0, name_bytes = 0;
+    uint64_t bad = 0; /* 1-based line of the range at which the parse failed */
+    const char *why = nullptr;
+};
+
+struct VmapKey {
+    const char *p; size_t n;
+    bool operator==(const VmapKey &o) const { return n == o.n && (n == 0 || memcmp(p, o.p, n) == 0); }
+};
+struct VmapKeyHash {
+    size_t operator()(const VmapKey &k) const
+    {
+        uint64_t h = 0xcbf29ce484222325ull; /* FNV-1a */
+        for (size_t i = 0; i < k.n; i++) h = (h ^ (unsigned char)k.p[i]) * 0x100000001b3ull;
+        return (size_t)h;
+    }
+};
+
+struct ntl_vmap {
+    int fd = -1;
+    bool eof = false;
+    char *buf = nullptr;
+    size_t cap = 0, size_hint = 0, have = 0, used = 0; /* as in ntl_tsv */
+    uint64_t lines_before = 0;                         /* lines of the blocks already handed out */
+    std::string ctg_blob;
+    std::unordered_map<VmapKey, uint32_t, VmapKeyHash> ctg;
+    std::vector<VmapRange> ranges;
+    std::string err;
+};
+
+struct VmapCount {
+    uint64_t n_reads = 0, n_maps = 0, n_hits = 0, name_bytes = 0;
+    void read(const char *, size_t n) { n_reads++; name_bytes += n; }
+    void map(uint32_t, uint32_t) { n_maps++; }
+    void hit(uint32_t, uint8_t, uint32_t, uint8_t) { n_hits++; }
+    void end_map() {}
+};
+struct VmapWrite {
+    char *names; uint64_t *name_off; uint32_t *map_off; ntl_mapping *maps; uint32_t *anchors; ntl_hit *hits;
+    uint64_t r, m, h, nb; /* reads, lines, hits and name bytes in front of the next one (of the block) */
+    void read(const char *p, size_t n)
+    {
+        if (r) map_off[r] = (uint32_t)m;
+        memcpy(names + nb, p, n); nb += n;
+        name_off[r + 1] = nb;
+        r++;
+    }
+    void map(uint32_t ctg, uint32_t anc)
+    {
+        maps[m].read = (uint32_t)(r - 1); maps[m].ctg = ctg; maps[m].n_hits = 0; maps[m].pad = 0; maps[m].hit_off = h;
+        anchors[m] = anc;
+    }
+    void hit(uint32_t cp, uint8_t cs, uint32_t rp, uint8_t rs)
+    {
+        ntl_hit &o = hits[h++];
+        o.ctg_pos = cp; o.read_pos = rp; o.ctg_strand = cs; o.read_strand = rs; o.pad[0] = o.pad[1] = 0;
+        maps[m].n_hits++;
+    }
+    void end_map() { m++; }
+};
+
+/* digits in [q, e) up to a byte that is none; false without a digit or above 2^32 - 1 */
+static inline bool vmap_u32(const char *&q, const char *e, uint32_t &out)
+{
+    uint64_t v = 0;
+    const char *s0 = q;
+    while (q < e && *q >= '0' && *q <= '9') {
+        v = v * 10 + (uint64_t)(*q - '0');
+        if (v > 0xFFFFFFFFull) return false;
+        q++;
+    }
+    out = (uint32_t)v;
+    return q > s0;
+}
+
+/* the stripped line [a, b) of the one that starts at p; returns the start of the next line */
+static inline const char *vmap_line(const char *p, const char *e, const char *&a, const char *&b)
+{
+    const char *nl = (const char *)memchr(p, '\n', (size_t)(e - p));
+    a = p; b = nl ? nl : e;
+    while (a < b && tsv_space(*a)) a++;
+    while (b > a && tsv_space(b[-1])) b--;
+    return nl ? nl + 1 : e;
+}
+
+/* the first column of a stripped line */
+static inline size_t vmap_id_len(const char *a, const char *b)
+{
+    const char *t = (const char *)memchr(a, '\t', (size_t)(b - a));
+    return (size_t)((t ? t : b) - a);
+}
+
+/* parses the lines of [p, e) (a range that starts at a read's first line); 0, or the 1-based line that is malformed and why */
+template <typename Sink>
+static uint64_t vmap_parse(const ntl_vmap *r, const char *p, const char *e, Sink &out, const char **why)
+{
+    uint64_t line_no = 0;
+    const char *cur = nullptr; /* the current read's id */
+    size_t cur_n = 0;
+    while (p < e) {
+        const char *a, *b;
+        p = vmap_line(p, e, a, b);
+        line_no++;
+        const char *t1 = (const char *)memchr(a, '\t', (size_t)(b - a));
+        const char *t2 = t1 ? (const char *)memchr(t1 + 1, '\t', (size_t)(b - t1 - 1)) : nullptr;
+        const char *t3 = t2 ? (const char *)memchr(t2 + 1, '\t', (size_t)(b - t2 - 1)) : nullptr;
+        if (!t3 || memchr(t3 + 1, '\t', (size_t)(b - t3 - 1))) { *why = "not four tab-separated fields"; return line_no; }
+        const size_t id_n = (size_t)(t1 - a);
+        if (!cur || id_n != cur_n || memcmp(a, cur, id_n) != 0) {
+            cur = a; cur_n = id_n;
+            out.read(a, id_n);
+        }
+        auto it = r->ctg.find(VmapKey{t1 + 1, (size_t)(t2 - t1 - 1)});
+        const char *q = t2 + 1;
+        uint32_t anc = 0;
+        if (!vmap_u32(q, t3, anc) || q != t3) { *why = "column 3 is not a number up to 4294967295"; return line_no; }
+        out.map(it == r->ctg.end() ? 0xFFFFFFFFu : it->second, anc);
+        q = t3 + 1;
+        for (;;) { /* split(" "): an empty token is malformed, and so is an empty column */
+            uint32_t cp = 0, rp = 0;
+            *why = "a token is not ctgpos:strand_readpos:strand with positions up to 4294967295";
+            if (!vmap_u32(q, b, cp) || b - q < 3 || q[0] != ':' || (q[1] != '+' && q[1] != '-') || q[2] != '_') return line_no;
+            const uint8_t cs = q[1] == '+';
+            q += 3;
+            if (!vmap_u32(q, b, rp) || b - q < 2 || q[0] != ':' || (q[1] != '+' && q[1] != '-')) return line_no;
+            out.hit(cp, cs, rp, (uint8_t)(q[1] == '+'));
+            q += 2;
+            if (q == b) break;
+            if (*q != ' ') return line_no;
+            q++;
+        }
+        *why = nullptr;
+        out.end_map();
+    }
+    return 0;
+}
+
+extern "C" int ntl_vmap_open(const char *path, const char *ctg_names, const uint64_t *ctg_name_off, uint64_t n_ctg, ntl_vmap **out)
+{
+    if (!path || !out || (n_ctg && !ctg_name_off) || n_ctg >= 0xFFFFFFFFull) return NTL_EINVAL;
+    *out = nullptr;
+    if (n_ctg && (ctg_name_off[n_ctg] < ctg_name_off[0] || (ctg_name_off[n_ctg] > ctg_name_off[0] && !ctg_names))) return NTL_EINVAL;
+    for (uint64_t i = 0; i < n_ctg; i++)
+        if (ctg_name_off[i + 1] < ctg_name_off[i]) return NTL_EINVAL;
+    int fd = strcmp(path, "-") == 0 ? dup(0) : open(path, O_RDONLY);
+    if (fd < 0) return NTL_EINVAL;
+    ntl_vmap *r = new ntl_vmap();
+    r->fd = fd;
+    widen_pipe(fd);
+    if (n_ctg) {
+        const uint64_t base = ctg_name_off[0];
+        r->ctg_blob.assign(ctg_names ? ctg_names + base : "", (size_t)(ctg_name_off[n_ctg] - base));
+        r->ctg.reserve((size_t)n_ctg * 2);
+        for (uint64_t i = 0; i < n_ctg; i++) /* the first of two equal names keeps its number */
+            r->ctg.emplace(VmapKey{r->ctg_blob.data() + (ctg_name_off[i] - base), (size_t)(ctg_name_off[i + 1] - ctg_name_off[i])}, (uint32_t)i);
+    }
+    struct stat st;
+    if (fstat(fd, &st) == 0 && S_ISREG(st.st_mode)) r->size_hint = (size_t)st.st_size + 1;
+    *out = r;
+    return NTL_OK;
+}
+
+extern "C" void ntl_vmap_close(ntl_vmap *r)
+{
+    if (!r) return;
+    if (r->fd >= 0) close(r->fd);
+    if (r->buf) buf_cache().give(r->buf, r->cap);
+    delete r;
+}
+
+extern "C" const char *ntl_vmap_error(const ntl_vmap *r) { return r ? r->err.c_str() : "no reader"; }
+
+extern "C" void ntl_vmap_sizes(const ntl_vmap *r, uint64_t *n_reads, uint64_t *n_maps, uint64_t *n_hits, uint64_t *name_bytes)
+{
+    uint64_t a = 0, b = 0, c = 0, d = 0;
+    if (r) for (auto &g : r->ranges) { a += g.n_reads; b += g.n_maps; c += g.n_hits; d += g.name_bytes; }
+    if (n_reads) *n_reads = a;
+    if (n_maps) *n_maps = b;
+    if (n_hits) *n_hits = c;
+    if (name_bytes) *name_bytes = d;
+}
+
+/* the first line start at or behind g in [lo, e) whose id differs from the line in front of it (e when there is none): a place where
+ * a range may begin.  lo is a line start. */
+static const char *vmap_read_start(const char *lo, const char *g, const char *e)
+{
+    if (g <= lo) return lo;
+    const char *prev = g - 1; /* the line that holds byte g - 1 */
+    while (prev > lo && prev[-1] != '\n') prev--;
+    const char *pa, *pb;
+    const char *p = vmap_line(prev, e, pa, pb);
+    while (p < e) {
+        const char *a, *b;
+        const char *nx = vmap_line(p, e, a, b);
+        const size_t n = vmap_id_len(a, b), pn = vmap_id_len(pa, pb);
+        if (n != pn || memcmp(a, pa, n) != 0) return p;
+        pa = a; pb = b; p = nx;
+    }
+    return e;
+}
+
+extern "C" int ntl_vmap_next(ntl_vmap *r, uint64_t max_bytes, uint64_t *n_reads)
+{
+    if (!r || !n_reads) return NTL_EINVAL;
+    *n_reads = 0;
+    if (!r->err.empty()) return NTL_EINVAL; /* a malformed file stays refused */
+    if (r->used) {
+        for (auto &g : r->ranges) r->lines_before += g.n_maps; /* every line of a block that parsed is one mapping */
+        memmove(r->buf, r->buf + r->used, r->have - r->used); r->have -= r->used; r->used = 0;
+    }
+    r->ranges.clear();
+    for (;;) {
+        const size_t target = max_bytes ? (size_t)max_bytes : (size_t)-1;
+        while (!r->eof && r->have < target) {
+            if (r->cap == r->have) {
+                size_t want_cap = r->cap ? r->cap * 2 : std::max<size_t>((size_t)8 << 20, max_bytes ? (size_t)max_bytes + (1u << 20) : r->size_hint);
+                size_t got = 0;
+                char *nb = buf_cache().take(want_cap, &got);
+                if (!nb) { r->err = "out of memory"; return NTL_ENOMEM; }
+                if (r->have) memcpy(nb, r->buf, r->have);
+                if (r->buf) buf_cache().give(r->buf, r->cap);
+                r->buf = nb; r->cap = got;
+            }
+            const size_t want = std::min(r->cap - r->have, target - r->have);
+            const ssize_t n = read(r->fd, r->buf + r->have, want);
+            if (n < 0) { r->err = "read error"; return NTL_EINVAL; }
+            if (n == 0) { r->eof = true; break; }
+            r->have += (size_t)n;
+        }
+        if (r->have == 0) return NTL_OK;
+        size_t end = r->have;
+        if (!r->eof) { /* whole lines, and not the last read: its lines may go on behind what was read */
+            while (end > 0 && r->buf[end - 1] != '\n') end--;
+            if (end) {
+                const char *last = r->buf + end - 1; /* the last whole line */
+                while (last > r->buf && last[-1] != '\n') last--;
+                const char *la, *lb;
+                vmap_line(last, r->buf + end, la, lb);
+                const size_t ln = vmap_id_len(la, lb);
+                while (last > r->buf) {
+                    const char *before = last - 1;
+                    while (before > r->buf && before[-1] != '\n') before--;
+                    const char *a, *b;
+                    vmap_line(before, last, a, b);
+                    if (vmap_id_len(a, b) != ln || memcmp(a, la, ln) != 0) break;
+                    last = before;
+                }
+                end = (size_t)(last - r->buf);
+            }
+            if (end == 0) { /* one read longer than the block: read on */
+                max_bytes = max_bytes ? max_bytes * 2 : 0;
+                continue;
+            }
+        }
+        r->used = end;
+        break;
+    }
+    const char *p0 = r->buf, *pe = p0 + r->used;
+    const size_t span = r->used;
+    size_t min_chunk = 1u << 20;
+    if (const char *e = getenv("NTL_IO_MIN_CHUNK")) { long v = atol(e); if (v > 0) min_chunk = (size_t)v; }
+    const unsigned T = (unsigned)std::min<size_t>(io_threads(), std::max<size_t>(1, span / min_chunk));
+    r->ranges.resize(T);
+    const char *prev = p0;
+    for (unsigned t = 0; t < T; t++) {
+        const char *nxt = t + 1 < T ? vmap_read_start(prev, std::max(prev, p0 + span / T * (t + 1)), pe) : pe;
+        r->ranges[t].b = prev; r->ranges[t].e = nxt;
+        prev = nxt;
+    }
+    run_threads(T, [&](size_t t) {
+        VmapRange &g = r->ranges[t];
+        VmapCount c;
+        g.bad = vmap_parse(r, g.b, g.e, c, &g.why);
+        g.n_reads = c.n_reads; g.n_maps = c.n_maps; g.n_hits = c.n_hits; g.name_bytes = c.name_bytes;
+    });
+    uint64_t lines = r->lines_before;
+    for (auto &g : r->ranges) {
+        if (g.bad) {
+            r->err = "line " + std::to_string(lines + g.bad) + ": " + g.why;
+            r->ranges.clear(); r->used = 0;
+            return NTL_EINVAL;
+        }
+        lines += g.n_maps;
+    }
+    uint64_t n_maps = 0;
+    ntl_vmap_sizes(r, n_reads, &n_maps, nullptr, nullptr);
+    if (n_maps >= 0xFFFFFFFFull) {
+        r->err = "more than 2^32 - 1 lines in one block: read with a smaller max_bytes";
+        r->ranges.clear(); r->used = 0;
+        return NTL_EINVAL;
+    }
+    return NTL_OK;
+}
+
+extern "C" int ntl_vmap_copy(const ntl_vmap *r, char *names, uint64_t *name_off, uint32_t *map_off, ntl_mapping *maps, uint32_t *anchors,
+                             ntl_hit *hits)
+{
+    if (!r || !name_off || !map_off) return NTL_EINVAL;
+    const size_t T = r->ranges.size();
+    std::vector<uint64_t> r0(T + 1, 0), m0(T + 1, 0), h0(T + 1, 0), n0(T + 1, 0);
+    for (size_t t = 0; t < T; t++) {
+        r0[t + 1] = r0[t] + r->ranges[t].n_reads;
+        m0[t + 1] = m0[t] + r->ranges[t].n_maps;
+        h0[t + 1] = h0[t] + r->ranges[t].n_hits;
+        n0[t + 1] = n0[t] + r->ranges[t].name_bytes;
+    }
+    if ((m0[T] && (!maps || !anchors || !hits)) || (n0[T] && !names)) return NTL_EINVAL;
+    name_off[0] = 0; map_off[0] = 0;
+    map_off[r0[T]] = (uint32_t)m0[T];
+    run_threads(T, [&](size_t t) {
+        const VmapRange &g = r->ranges[t];
+        if (g.b == g.e) return;
+        VmapWrite w{names, name_off, map_off, maps, anchors, hits, r0[t], m0[t], h0[t], n0[t]};
+        if (r0[t]) map_off[r0[t]] = (uint32_t)m0[t]; /* the range's first read (VmapWrite::read writes the later ones) */
+        const char *why = nullptr;
+        vmap_parse(r, g.b, g.e, w, &why);
     });
     return NTL_OK;
 }

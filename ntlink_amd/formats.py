@@ -167,12 +167,12 @@ def write_paf(fh, res, read_names, read_len, ctg_names, ctg_len, read_base=0):
                  f"{ctg_names[c]}\t{int(ctg_len[c])}\t{ts}\t{te}\t{n}\t{te - ts}\t255\n")
 
 
-def parse_verbose(fh):
+def parse_verbose(fh, with_anchors=False):
     """Checkpoint reader (bin/ntlink_pair.py:437-488, bin/ntlink_utils.py:296-305): yields
-    (read_id, [(contig, [(ctg_pos, ctg_strand, read_pos, read_strand), ...]), ...]) per read."""
+    (read_id, [(contig, [(ctg_pos, ctg_strand, read_pos, read_strand), ...]), ...]) per read; with_anchors: (contig, hits, int(column 3))."""
     cur, entries = None, []
     for line in fh:
-        read_id, contig, _n, mx = line.strip().split("\t")
+        read_id, contig, n_anchors, mx = line.strip().split("\t")
         hl = []
         for tok in mx.split(" "):
             c, r = tok.split("_")
@@ -183,6 +183,47 @@ def parse_verbose(fh):
             if cur is not None:
                 yield cur, entries
             cur, entries = read_id, []
-        entries.append((contig, hl))
+        entries.append((contig, hl, int(n_anchors)) if with_anchors else (contig, hl))
     if cur is not None:
         yield cur, entries
+
+
+class VerboseBlock:
+    """One block of read_verbose: names (seqio.Names, one per read), map_off u32[n_reads + 1], maps (capi.MAPPING_DT: read = the read's
+    number in the block, ctg = the contig's number or capi.NO_CTG), anchors u32 (column 3) and hits (capi.HIT_DT)."""
+    __slots__ = ("names", "map_off", "maps", "anchors", "hits")
+
+    def __init__(self, names, map_off, maps, anchors, hits):
+        self.names, self.map_off, self.maps, self.anchors, self.hits = names, map_off, maps, anchors, hits
+
+
+def read_verbose(path, ctg_names, max_bytes=0, lib_path=None):
+    """Native reader of <prefix>.verbose_mapping.tsv for the gap filler (csrc/ntl_io.cpp, ntl_vmap_*; read_verbose_mappings,
+    bin/ntlink_patch_gaps.py:178-198): yields a VerboseBlock per about max_bytes of text (0: the whole file); a read's lines are never
+    split.  ctg_names: the contig table (seqio.Names or a list); a malformed line raises ValueError with its line number."""
+    from . import capi
+    L = capi.load(lib_path)
+    nm = Names.of(ctg_names)
+    blob, noff = np.ascontiguousarray(nm.blob), np.ascontiguousarray(nm.off, np.uint64)
+    h = C.c_void_p()
+    if L.ntl_vmap_open(path.encode(), blob.ctypes.data if len(blob) else None, _p(noff, C.c_uint64), len(nm), C.byref(h)) != 0:
+        raise OSError(f"cannot open {path}")
+    try:
+        while True:
+            n = C.c_uint64()
+            if L.ntl_vmap_next(h, int(max_bytes), C.byref(n)) != 0:
+                raise ValueError(f"{path}: {L.ntl_vmap_error(h).decode()}")
+            n = n.value
+            if n == 0:
+                return
+            nmaps, nhits, nb = C.c_uint64(), C.c_uint64(), C.c_uint64()
+            L.ntl_vmap_sizes(h, None, C.byref(nmaps), C.byref(nhits), C.byref(nb))
+            names, name_off = np.empty(nb.value, np.uint8), np.empty(n + 1, np.uint64)
+            map_off, maps = np.empty(n + 1, np.uint32), np.empty(nmaps.value, capi.MAPPING_DT)
+            anchors, hits = np.empty(nmaps.value, np.uint32), np.empty(nhits.value, capi.HIT_DT)
+            if L.ntl_vmap_copy(h, names.ctypes.data, name_off.ctypes.data, map_off.ctypes.data, maps.ctypes.data, anchors.ctypes.data,
+                               hits.ctypes.data) != 0:
+                raise ValueError(f"{path}: copy failed")
+            yield VerboseBlock(Names(names, name_off), map_off, maps, anchors, hits)
+    finally:
+        L.ntl_vmap_close(h)

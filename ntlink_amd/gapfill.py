@@ -27,13 +27,22 @@ and ``scaffolds``.
 
 * a gap whose two names come out equal has ONE contig in the reference's dict, so ``len(accepted_anchor_contigs) != 2`` whatever
   maps: its status is NTL_GAP_NOT_TWO without any mapping (the grouped call, which keeps the two records apart, is overruled)
+
+In front of all that stands the choice of every gap's read (:94-111, 149-198, 232-261, 311-342): ``read_path_file_pairs`` and
+``choose_gap_reads(pairs, mappings_filename, sequences, args)``, the drop-in for read_verbose_mappings, choose_best_read_per_pair and
+find_masking_cut_points in a row.  The verbose file is read block by block by the native reader (formats.read_verbose, ntl_vmap_*), one
+device pass per block (Device.gap_select, ntl_gap_select, csrc/gap_select_kernels.h) returns a 32-byte record per (pair, supporting
+read) and nothing else, and the host keeps per pair the running best: anchor sum descending, then read id descending as a string.
+``choose_gap_reads_restated`` is the three reference functions restated over formats.parse_verbose; the tests and
+tools/gapmap_bench.py compare against it, nothing falls back to it.
 """
 import collections
+import itertools
 import re
 
 import numpy as np
 
-from . import anchor, capi, seqio
+from . import anchor, capi, formats, seqio
 from .anchor import ContigRun, Minimizer, MinimizerPositions
 
 _STRAND = ("-", "+")
@@ -300,3 +309,205 @@ def map_gap_reads(scaffolds_fasta, reads_fasta, k, w, args, dev=None, with_minim
     A scaffold count other than twice the read count raises ValueError."""
     return _map_records(_records_of(scaffolds_fasta, batch_bases), _records_of(reads_fasta, batch_bases), k, w, args, dev,
                         with_minimizers, name_of, batch_bases)
+
+
+# ---------------------------------------------------------------- the read of every gap (bin/ntlink_patch_gaps.py:94-111, 149-261, 311-342)
+
+VERBOSE_BLOCK_BYTES = 64 << 20  # text per device pass of choose_gap_reads (a read's lines are never split)
+_GAP = re.compile(r"^(\d+)N$")  # :97
+
+
+class PairInfo:
+    """A pair of the path file with the reference's fields (:55-65)"""
+
+    def __init__(self, gap_size):
+        self.gap_size = int(gap_size)
+        self.mapping_reads = set()
+        self.chosen_read = None
+        self.source_ctg_cut = None
+        self.source_read_cut = None
+        self.target_ctg_cut = None
+        self.target_read_cut = None
+        self.old_anchor_used = False
+
+
+def read_path_file_pairs(path_filename, min_gap_size):
+    """read_path_file_pairs (:94-111): (source node, target node) -> PairInfo for every `<n>N` between two nodes with n > min_gap_size;
+    abyss-scaffold's gap is one more than the estimate"""
+    pairs = {}
+    with open(path_filename, "r") as fin:
+        for line in fin:
+            line = line.strip().split("\t")
+            if len(line) < 2:
+                continue
+            _, path = line
+            path = path.split(" ")
+            for idx in range(len(path) - 2):
+                i, j, k = path[idx:idx + 3]
+                gap_match = _GAP.search(j)
+                if gap_match and int(gap_match.group(1)) > min_gap_size:
+                    pairs[(i, k)] = PairInfo(int(gap_match.group(1)) - 1)
+    return pairs
+
+
+def _node(node):
+    if node[-1:] not in ("+", "-"):
+        raise ValueError("+ or - needed for last character of node, found " + node[-1:])  # reverse_complement_pair (:130-146)
+    return node[:-1], node[-1] == "-"
+
+
+def pair_tables(pairs, sequences):
+    """What the device pass needs of the path's pairs: (contig names, ctg_len u32, keys u64) -- the contigs the pairs name, in order of
+    first appearance, and per pair its key in ntl_gap_select's table.  KeyError for a contig that is not in `sequences`."""
+    number, names, lengths, keys = {}, [], [], []
+    for source, target in pairs:
+        nodes = []
+        for node in (source, target):
+            name, minus = _node(node)
+            if name not in number:
+                number[name] = len(names)
+                names.append(name)
+                lengths.append(int(sequences[name].length))
+            nodes.append((number[name], minus))
+        keys.append(capi.pair_key(nodes[0][0], nodes[0][1], nodes[1][0], nodes[1][1]))
+    return names, np.array(lengths, np.uint32), np.array(keys, np.uint64)
+
+
+def gap_candidates(mappings_filename, ctg_names, ctg_len, keys, large_k, dev=None, max_bytes=VERBOSE_BLOCK_BYTES):
+    """Per block of the verbose file: (VerboseBlock, capi.GAP_CAND_DT records) -- every (pair, supporting read) of the block with its
+    anchor sum, flags and the cuts the read would give."""
+    dev = dev or anchor._default_device()
+    table = capi.pair_table(keys, lib_path=dev.lib_path)
+    for block in formats.read_verbose(mappings_filename, ctg_names, max_bytes=max_bytes, lib_path=dev.lib_path):
+        yield block, dev.gap_select(block, ctg_len, large_k, table)
+
+
+def choose_gap_reads(pairs, mappings_filename, sequences, args, dev=None, max_bytes=VERBOSE_BLOCK_BYTES):
+    """read_verbose_mappings, choose_best_read_per_pair and find_masking_cut_points of the reference in a row (:178-198, 249-261,
+    311-342): fills ``mapping_reads`` of every pair and sets ``chosen_read`` and the four cuts of every pair that has a valid supporting
+    read.  pairs: what read_path_file_pairs returns; sequences: name -> object with ``.length``; args: ``.large_k``.
+
+    * KeyError, before anything is read, for a pair whose contig is not in ``sequences``
+    * AssertionError where the reference's ``assert a >= 0`` / ``assert b >= 0`` (:222-223) fails on a read it reaches: a pair whose
+      best read among the valid and the negative ones is a negative one
+    * ValueError for a read id that supports pairs from two separate groups of lines (the reference overwrites the first silently),
+      and for a malformed line (with its number)"""
+    ctg_names, ctg_len, keys = pair_tables(pairs, sequences)
+    infos = list(pairs.values())
+    best = [None] * len(infos)  # per pair (anchor sum, read id, negative, the four cuts) of the first read the reference would stop at
+    seen = {}                   # read id -> (block, read) among the reads that gave a candidate
+    stop = capi.NTL_GAPSEL_VALID | capi.NTL_GAPSEL_NEGATIVE
+    for b, (block, cands) in enumerate(gap_candidates(mappings_filename, ctg_names, ctg_len, keys, int(args.large_k), dev, max_bytes)):
+        if not len(cands):
+            continue
+        raw, off = block.names.blob.tobytes(), block.names.off
+        ids = {}
+        for pair, read, anchors, flags, sc, sr, tc, tr in cands.tolist():
+            rid = ids.get(read)
+            if rid is None:
+                rid = ids[read] = raw[int(off[read]):int(off[read + 1])].decode()
+                if seen.setdefault(rid, (b, read)) != (b, read):
+                    raise ValueError(f"{mappings_filename}: read {rid} supports pairs from two separate groups of lines")
+            infos[pair].mapping_reads.add(rid)
+            if flags & stop and (best[pair] is None or (anchors, rid) > best[pair][:2]):
+                best[pair] = (anchors, rid, bool(flags & capi.NTL_GAPSEL_NEGATIVE), sc, sr, tc, tr)
+    for (source, target), info, got in zip(pairs, infos, best):
+        if got is None:
+            continue
+        assert not got[2], f"pair {source} {target}, read {got[1]}: a negative distance to a contig end (calculate_est_gap_size)"
+        info.chosen_read = got[1]
+        info.source_ctg_cut, info.source_read_cut, info.target_ctg_cut, info.target_read_cut = got[3:]
+
+
+# The same in plain Python, as the reference has it: the comparison for the tests and for tools/gapmap_bench.py, never a fallback.
+
+def _reverse_complement_pair(source, target):
+    """:130-146"""
+    flip = {"+": "-", "-": "+"}
+    return target[:-1] + flip[target[-1]], source[:-1] + flip[source[-1]]
+
+
+def _restated_mappings(mappings_filename):
+    """per read of the file (id, mapping dict, mapping order) as tally_contig_mapping_info builds them (:149-163): contig -> (anchors,
+    hits, orientation) of the valid mappings and "length" """
+    with open(mappings_filename) as fh:
+        for read_id, entries in formats.parse_verbose(fh, with_anchors=True):
+            info, order = {}, []
+            for ctg, hits, anchors in entries:
+                if all(h[1] == h[3] for h in hits):
+                    orientation = "+"
+                elif all(h[1] != h[3] for h in hits):
+                    orientation = "-"
+                else:
+                    continue
+                if not (all(a[0] < b[0] for a, b in zip(hits, hits[1:])) or all(a[0] > b[0] for a, b in zip(hits, hits[1:]))):
+                    continue
+                info[ctg] = (anchors, hits, orientation)
+                order.append(ctg + orientation)
+                info["length"] = hits[-1][2]
+            yield read_id, info, order
+
+
+def _restated_valid(source, target, info, sequences, k):
+    """is_valid_supporting_read with calculate_est_gap_size (:208-246) -> (valid, negative); the reference asserts where negative"""
+    if source[-1] != info[source[:-1]][2]:
+        assert target[-1] != info[target[:-1]][2]
+        source, target = _reverse_complement_pair(source, target)
+    s_mx, t_mx = info[source[:-1]][1][-1], info[target[:-1]][1][0]
+    a = sequences[source[:-1]].length - s_mx[0] - k if source[-1] == "+" else s_mx[0]
+    b = t_mx[0] if target[-1] == "+" else sequences[target[:-1]].length - t_mx[0] - k
+    return abs(t_mx[2] - s_mx[2] - a - b) <= info["length"], a < 0 or b < 0
+
+
+def _restated_cuts(source, target, info, k):
+    """find_masking_cut_points for one pair and one read (:317-342)"""
+    _sa, s_hits, s_ori = info[source[:-1]]
+    _ta, t_hits, t_ori = info[target[:-1]]
+    s_mx = s_hits[-1] if s_ori == source[-1] else s_hits[0]
+    t_mx = t_hits[0] if t_ori == target[-1] else t_hits[-1]
+    ctg_cut = lambda pos, ori, sign: pos + k if ori == sign and sign == "-" else pos   # assign_ctg_cut (:291-299)
+    read_cut = lambda pos, ori, sign: pos + k if ori != sign and sign == "+" else pos  # assign_read_cut (:301-308)
+    return (ctg_cut(s_mx[0], s_ori, source[-1]), read_cut(s_mx[2], s_ori, source[-1]),
+            ctg_cut(t_mx[0], t_ori, target[-1]), read_cut(t_mx[2], t_ori, target[-1]))
+
+
+def restated_candidates(pairs, mappings_filename, sequences, large_k):
+    """The records ntl_gap_select must return for the whole file as one block (capi.GAP_CAND_DT; `read` counts the file's reads), and
+    the reads' ids"""
+    number = {pair: i for i, pair in enumerate(pairs)}
+    out, ids = [], []
+    for r, (read_id, info, order) in enumerate(_restated_mappings(mappings_filename)):
+        ids.append(read_id)
+        for i, j in itertools.combinations(order, 2):
+            for pair, via in (((i, j), 0), (_reverse_complement_pair(i, j), capi.NTL_GAPSEL_VIA_REVCOMP)):
+                if pair in number:
+                    valid, negative = _restated_valid(pair[0], pair[1], info, sequences, large_k)
+                    out.append((number[pair], r, info[pair[0][:-1]][0] + info[pair[1][:-1]][0],
+                                int(valid) | (capi.NTL_GAPSEL_NEGATIVE if negative else 0) | via, *_restated_cuts(pair[0], pair[1], info, large_k)))
+    return np.array(out, capi.GAP_CAND_DT), ids
+
+
+def choose_gap_reads_restated(pairs, mappings_filename, sequences, args):
+    """read_verbose_mappings, choose_best_read_per_pair and find_masking_cut_points (:178-198, 249-261, 311-342), dicts and all"""
+    mappings = {}
+    for read_id, info, order in _restated_mappings(mappings_filename):
+        added = False
+        for i, j in itertools.combinations(order, 2):
+            for pair in ((i, j), _reverse_complement_pair(i, j)):
+                if pair in pairs:
+                    pairs[pair].mapping_reads.add(read_id)
+                    added = True
+        if added:
+            mappings[read_id] = info
+    for (source, target), pair in pairs.items():
+        reads = [(read_id, mappings[read_id][source.strip("+-")][0], mappings[read_id][target.strip("+-")][0]) for read_id in pair.mapping_reads]
+        for read_id, _, _ in sorted(reads, key=lambda x: (np.mean([x[1], x[2]]), x[0]), reverse=True):
+            valid, negative = _restated_valid(source, target, mappings[read_id], sequences, args.large_k)
+            assert not negative
+            if valid:
+                pair.chosen_read = read_id
+                break
+    for (source, target), pair in pairs.items():
+        if pair.chosen_read is not None:
+            pair.source_ctg_cut, pair.source_read_cut, pair.target_ctg_cut, pair.target_read_cut = \
+                _restated_cuts(source, target, mappings[pair.chosen_read], args.large_k)

@@ -12,7 +12,13 @@ For G synthetic gaps (two scaffold ends of 300 .. 3000 bases, one read piece acr
             it -- gapfill.map_gap_reads and assess_accepted_anchor_contigs (bin/ntlink_patch_gaps.py:443-517) in Python over its Gap
             objects; both end states must be equal.  Also gap_cut_kernel alone (ntl_prof_get "gap_cut") and the bytes it reads: per gap
             two offsets, two signs and, with two mappings, their two records and 12 B per hit.
-Prints one JSON line per G (and one per G for --cuts)."""
+  select    (--select) the choice of every gap's read from the verbose mappings: a synthetic <prefix>.verbose_mapping.tsv of G gaps with
+            about 30 supporting reads each and ten times as many reads that support nothing, written by formats.write_verbose; best of
+            --repeat in one process: gapfill.choose_gap_reads, gapfill.choose_gap_reads_restated (the reference's three functions in
+            Python; both must leave the same fields in every pair), the three kernels of ntl_gap_select alone (ntl_prof_get
+            "gap_select": assess, count, scan with its host wait, fill) beside the bytes the block uploads, and the reader alone in
+            GB/s of text.
+Prints one JSON line per G (and one per G for --cuts / --select)."""
 import argparse
 import json
 import sys
@@ -24,7 +30,7 @@ import types
 import numpy as np
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from ntlink_amd import anchor, capi, gapfill  # noqa: E402
+from ntlink_amd import anchor, capi, formats, gapfill  # noqa: E402
 
 ACGT = np.frombuffer(b"ACGT", np.uint8)
 K, W = 20, 10
@@ -166,15 +172,102 @@ def cuts_leg(dev, G, repeat):
                       "device": dev.name}), flush=True)
 
 
+def make_verbose(path, G, per_gap=30, idle=10, seed=3):
+    """G + 1 contigs in a chain of G gaps; per gap `per_gap` reads that map to its two contigs in a row (3 .. 12 hits each, near the
+    gap) and per_gap * idle reads with one mapping somewhere; in random order, written by the project's emitter.  -> path text, lengths"""
+    rng = np.random.default_rng(seed)
+    LEN = 20000
+    n_sup, n_idle = G * per_gap, G * per_gap * idle
+    n_reads = n_sup + n_idle
+    is_sup = np.zeros(n_reads, bool)
+    is_sup[rng.permutation(n_reads)[:n_sup]] = True
+    gap_of = rng.integers(0, G, n_reads)
+    per_read = np.where(is_sup, 2, 1)
+    first = np.concatenate([[0], np.cumsum(per_read)])
+    n_maps = int(first[-1])
+    maps = np.zeros(n_maps, capi.MAPPING_DT)
+    maps["read"] = np.repeat(np.arange(n_reads), per_read)
+    second = np.zeros(n_maps, bool)
+    second[first[:-1][is_sup] + 1] = True
+    maps["ctg"] = np.repeat(gap_of, per_read) + second
+    maps["n_hits"] = rng.integers(3, 13, n_maps)
+    off = np.concatenate([[0], np.cumsum(maps["n_hits"])])
+    maps["hit_off"] = off[:-1]
+    idx = np.arange(int(off[-1])) - np.repeat(off[:-1], maps["n_hits"])
+    hits = np.zeros(int(off[-1]), capi.HIT_DT)
+    c0 = np.where(second, 100, LEN - 700)  # a source ends near its contig's end, a target starts near its start
+    hits["ctg_pos"] = np.repeat(c0, maps["n_hits"]) + 50 * idx
+    hits["read_pos"] = np.repeat(np.where(second, 2000, 1000), maps["n_hits"]) + 40 * idx
+    hits["ctg_strand"] = hits["read_strand"] = 1
+    with open(path, "w") as fh:
+        formats.write_verbose(fh, {"maps": maps, "hits": hits}, [f"r{i}" for i in range(n_reads)], [f"c{i}" for i in range(G + 1)])
+    return "".join(f"p{g}\tc{g}+ 500N c{g + 1}+\n" for g in range(G)), {f"c{i}": types.SimpleNamespace(length=LEN) for i in range(G + 1)}, int(off[-1])
+
+
+def select_leg(dev, G, repeat):
+    with tempfile.TemporaryDirectory() as tmp:
+        vp, pp = os.path.join(tmp, "g.verbose_mapping.tsv"), os.path.join(tmp, "g.path")
+        path_text, sequences, n_hits = make_verbose(vp, G)
+        with open(pp, "w") as fh:
+            fh.write(path_text)
+        text_bytes = os.path.getsize(vp)
+        args = argparse.Namespace(large_k=K)
+        state = lambda pairs: [(sorted(p.mapping_reads), p.chosen_read, p.source_ctg_cut, p.source_read_cut, p.target_ctg_cut, p.target_read_cut)
+                               for p in pairs.values()]
+        gapfill.choose_gap_reads(gapfill.read_path_file_pairs(pp, 20), vp, sequences, args, dev=dev)  # warm-up
+        t_new, t_old, states = [], [], []
+        for fn, times in ((lambda p: gapfill.choose_gap_reads(p, vp, sequences, args, dev=dev), t_new),
+                          (lambda p: gapfill.choose_gap_reads_restated(p, vp, sequences, args), t_old)):
+            for _ in range(repeat):
+                pairs = gapfill.read_path_file_pairs(pp, 20)
+                t0 = time.perf_counter()
+                fn(pairs)
+                times.append(time.perf_counter() - t0)
+            states.append(state(pairs))
+        assert states[0] == states[1], "the two ways leave different fields"
+        ctg_names, ctg_len, keys = gapfill.pair_tables(gapfill.read_path_file_pairs(pp, 20), sequences)
+        t_read = []
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            blocks = list(formats.read_verbose(vp, ctg_names, max_bytes=gapfill.VERBOSE_BLOCK_BYTES))
+            t_read.append(time.perf_counter() - t0)
+        table = capi.pair_table(keys)
+        dev.set_pipeline(False)
+        dev.prof_enable(True)
+        dev.prof_reset()
+        t_call, n_cand = [], 0
+        for _ in range(repeat):
+            t0 = time.perf_counter()
+            n_cand = sum(len(dev.gap_select(b, ctg_len, K, table)) for b in blocks)
+            t_call.append(time.perf_counter() - t0)
+        ms, launches = dev.prof_get("gap_select")
+        dev.prof_enable(False)
+        dev.set_pipeline(True)
+        up = sum(b.map_off.nbytes + b.maps.nbytes + b.anchors.nbytes + b.hits.nbytes for b in blocks) + len(blocks) * (ctg_len.nbytes + 12 * len(table[0]))
+        kernel_ms = ms / max(1, launches) * len(blocks)
+        print(json.dumps({"leg": "select", "gaps": G, "reads": sum(len(b.names) for b in blocks), "hits": n_hits, "text_bytes": text_bytes,
+                          "blocks": len(blocks), "candidates": n_cand, "chosen": sum(s[1] is not None for s in states[0]),
+                          "choose_gap_reads_s": min(t_new), "choose_gap_reads_s_all": t_new, "restated_s": min(t_old), "restated_s_all": t_old,
+                          "ratio": min(t_old) / min(t_new), "reader_s": min(t_read), "reader_GBps": text_bytes / min(t_read) / 1e9,
+                          "gap_select_call_s": min(t_call), "gap_select_kernels_ms": kernel_ms, "upload_bytes": up,
+                          "kernels_GBps_of_upload": up / kernel_ms / 1e6 if kernel_ms else None, "device": dev.name}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gaps", type=int, nargs="+", default=[2000, 20000])
     ap.add_argument("--per-gap", type=int, default=2000, help="gaps the per-gap loop runs over (scaled to G)")
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--cuts", action="store_true", help="the cuts leg alone: gapfill.map_long_reads beside map_gap_reads + the assess in Python")
+    ap.add_argument("--select", action="store_true", help="the select leg alone: gapfill.choose_gap_reads beside the three reference functions in Python")
     a = ap.parse_args()
     args = argparse.Namespace(k=K, z=1000, x=0.0, sensitive=False)
     dev = capi.Device(0)
+    if a.select:
+        for G in a.gaps:
+            select_leg(dev, G, a.repeat)
+        dev.close()
+        return
     if a.cuts:
         for G in a.gaps:
             cuts_leg(dev, G, a.repeat)
