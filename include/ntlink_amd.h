@@ -165,6 +165,28 @@ int ntl_synth_slices(ntl_ctx *ctx, const ntl_batch *src, uint64_t seed, uint64_t
                      double sub, double ins, double del, ntl_batch **out);
 int ntl_batch_download(const ntl_batch *b, char *seqs, uint64_t *offsets);
 
+/* ---- N-masked copies of resident records (the gap filler's temporary files, without the files) ---- */
+
+/* The reference's gap filler writes per gap the whole source scaffold, the whole target scaffold and the whole chosen read as text
+ * with everything but the scaffold end beside the gap / the read piece between its two cuts replaced by N
+ * (print_masked_sequences, bin/ntlink_patch_gaps.py:346-389; the reads it keeps for that: get_gap_fill_reads, :264-273) and reads
+ * the two files back for the re-mapping.  ntl_batch_mask makes the same records from a resident batch (csrc/mask_kernels.h):
+ * record i of *out has the FULL length of record src_seq[i] of src, holds that record's bases in [keep_lo[i], keep_hi[i]) and no
+ * valid base outside -- exactly what ntl_batch_create makes of the ASCII record with every byte outside the range replaced by N.
+ * Positions and the --len column stay in the source record's coordinates; every sketch and map call takes the result.
+ *   - src may hold several runs per record (N, IUPAC codes, lower case); the same record may be named any number of times
+ *   - an empty range, or one inside a non-ACGT stretch, gives a record without a run: it sketches to nothing
+ *   - NTL_EINVAL with a message: src_seq[i] >= the source's sequences, keep_lo[i] > keep_hi[i], keep_hi[i] > the record's length
+ *   - n == 0 gives an empty batch
+ * The call WAITS for the device (the run count comes back to the host in the middle of it): the caller's arrays are free when it
+ * returns and the batch is complete; src may be destroyed at once.  Event name for ntl_prof_get: "batch_mask".
+ *
+ * ntl_batch_download_n: ntl_batch_download for ANY batch -- upper-case ASCII with N wherever no run covers a base (lower case and
+ * IUPAC codes of the input are not kept by a batch: they come back as upper case and as N). */
+int ntl_batch_mask(ntl_ctx *ctx, const ntl_batch *src, uint64_t n, const uint32_t *src_seq, const uint32_t *keep_lo,
+                   const uint32_t *keep_hi, ntl_batch **out);
+int ntl_batch_download_n(const ntl_batch *b, char *seqs, uint64_t *offsets);
+
 /* ---- sketch ---------------------------------------------------------------------------- */
 
 /* Asynchrony.  ntl_sketch_run[_indexed] and ntl_map_run only QUEUE device work and return; no size comes back to the host

@@ -20,7 +20,7 @@ SYMBOLS = [
     "ntl_ctx_create", "ntl_ctx_destroy", "ntl_last_error", "ntl_ctx_device_name", "ntl_ctx_sync", "ntl_ctx_pipelined", "ntl_ctx_set_pipeline",
     "ntl_prof_enable", "ntl_prof_reset", "ntl_prof_get",
     "ntl_batch_create", "ntl_batch_create_packed", "ntl_batch_create_packed_at", "ntl_packed_words", "ntl_batch_destroy", "ntl_batch_nseq", "ntl_batch_bases", "ntl_host_alloc", "ntl_host_free",
-    "ntl_synth_genome", "ntl_synth_slices", "ntl_batch_download",
+    "ntl_synth_genome", "ntl_synth_slices", "ntl_batch_download", "ntl_batch_mask", "ntl_batch_download_n",
     "ntl_sketch_run", "ntl_sketch_run_indexed", "ntl_sketch_run_for_map", "ntl_sketch_has_records", "ntl_sketch_destroy", "ntl_sketch_nseq", "ntl_sketch_count", "ntl_sketch_download",
     "ntl_sketch_strips", "ntl_sketch_redo_strips", "ntl_sketch_fallback_strips", "ntl_sketch_from_lists", "ntl_sketch_plan", "ntl_sketch_wait", "ntl_mapres_wait",
     "ntl_sketch_from_host", "ntl_overlap_filter",
@@ -128,6 +128,8 @@ def load(path=None):
     L.ntl_synth_slices.argtypes = [vp, vp, C.c_uint64, C.c_uint64, u32p, u32p, u32p, u8p, C.c_double, C.c_double, C.c_double,
                                    C.POINTER(vp)]
     L.ntl_batch_download.argtypes = [vp, vp, u64p]
+    L.ntl_batch_mask.argtypes = [vp, vp, C.c_uint64, u32p, u32p, u32p, C.POINTER(vp)]
+    L.ntl_batch_download_n.argtypes = [vp, vp, u64p]
     L.ntl_sketch_run.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.ntl_sketch_run_indexed.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
     L.ntl_sketch_run_for_map.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
@@ -287,6 +289,14 @@ class Batch(_Handle):
         off = np.zeros(self.nseq + 1, np.uint64)
         self.dev._chk(self.dev.L.ntl_batch_download(self.ptr, buf.ctypes.data, _ptr(off, C.c_uint64)))
         return buf[:self.bases], off
+
+    def download_n(self):
+        """(ASCII bases uint8, offsets u64[nseq+1]) of any batch (ntl_batch_download_n): upper case, N wherever no ACGT run covers a
+        base -- a masked stretch, an N or an IUPAC code of the input."""
+        off = np.zeros(self.nseq + 1, np.uint64)
+        buf = np.empty(max(self.bases, 1), np.uint8)
+        self.dev._chk(self.dev.L.ntl_batch_download_n(self.ptr, buf.ctypes.data, _ptr(off, C.c_uint64)))
+        return buf[:int(off[-1])], off
 
 
 class Sketch(_Handle):
@@ -627,6 +637,20 @@ class Device:
         self._chk(self.L.ntl_synth_slices(self.ptr, src.ptr, int(seed), len(ln), _ptr(sq, C.c_uint32), _ptr(st, C.c_uint32),
                                           _ptr(ln, C.c_uint32), None if rv is None else _ptr(rv, C.c_uint8),
                                           float(sub), float(ins), float(dele), C.byref(p)))
+        return Batch(self, p)
+
+    def batch_mask(self, src, src_seq, keep_lo, keep_hi):
+        """N-masked full-length copies of records of the resident batch `src` (ntl_batch_mask, csrc/mask_kernels.h): record i of the
+        result is record src_seq[i] with every base outside [keep_lo[i], keep_hi[i]) replaced by N -- what the reference's
+        print_masked_sequences writes to its temporary files, made where the bases already are.  Positions stay in the source
+        record's coordinates.  The call waits for the device; the arrays and `src` may go once it returns."""
+        sq = np.ascontiguousarray(src_seq, np.uint32); lo = np.ascontiguousarray(keep_lo, np.uint32)
+        hi = np.ascontiguousarray(keep_hi, np.uint32)
+        if sq.ndim != 1 or not (sq.shape == lo.shape == hi.shape):
+            raise ValueError("src_seq, keep_lo and keep_hi must have one entry per output record each")
+        p = C.c_void_p()
+        self._chk(self.L.ntl_batch_mask(self.ptr, src.ptr, len(sq), _ptr(sq, C.c_uint32), _ptr(lo, C.c_uint32), _ptr(hi, C.c_uint32),
+                                        C.byref(p)))
         return Batch(self, p)
 
     def sketch(self, batch, k, w, index=None, records=True):

@@ -36,6 +36,7 @@
 #include "gap_select_kernels.h"
 #include "pack_kernels.h"
 #include "synth_kernels.h"
+#include "mask_kernels.h"
 #include "overlap_kernels.h"
 #include "format_kernels.h"
 
@@ -848,6 +849,118 @@ extern "C" int ntl_batch_download(const ntl_batch *b, char *seqs, uint64_t *off)
         HIPCHK(c, hipMemcpyAsync(seqs + p0, tmp.p, m, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    return NTL_OK;
+}
+
+/* ------------------------------------------------------------------ masked copies --------- */
+
+/* N-masked full-length copies of resident records (mask_kernels.h; print_masked_sequences of the reference,
+ * bin/ntlink_patch_gaps.py:346-389, without its two files).  Waits for the device before it returns: the number of runs comes back
+ * to the host for the run tables' size in the middle of it, and the caller's arrays are free afterwards. */
+extern "C" int ntl_batch_mask(ntl_ctx *c, const ntl_batch *src, uint64_t n, const uint32_t *src_seq, const uint32_t *keep_lo,
+                              const uint32_t *keep_hi, ntl_batch **out)
+{
+    if (!c || !src || !out || (n && (!src_seq || !keep_lo || !keep_hi))) return NTL_EINVAL;
+    *out = nullptr;
+    if (n >= ((uint64_t)1 << 31)) return fail(c, NTL_EINVAL, "too many sequences in one batch");
+    std::vector<uint64_t> seq_base(n + 1);
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n; i++) {
+        if (src_seq[i] >= src->nseq)
+            return fail(c, NTL_EINVAL, "record " + std::to_string(i) + ": source sequence index " + std::to_string(src_seq[i]) + " out of range (" +
+                                       std::to_string(src->nseq) + " sequences)");
+        if (keep_lo[i] > keep_hi[i])
+            return fail(c, NTL_EINVAL, "record " + std::to_string(i) + ": keep_lo " + std::to_string(keep_lo[i]) + " is above keep_hi " +
+                                       std::to_string(keep_hi[i]));
+        if (keep_hi[i] > src->seq_len[src_seq[i]])
+            return fail(c, NTL_EINVAL, "record " + std::to_string(i) + ": keep_hi " + std::to_string(keep_hi[i]) + " is beyond the source sequence's " +
+                                       std::to_string(src->seq_len[src_seq[i]]) + " bases");
+        seq_base[i] = NTL_LEAD_PAD + total;
+        total += src->seq_len[src_seq[i]];
+    }
+    seq_base[n] = NTL_LEAD_PAD + total;
+    if (total >= 0xFFFFFFF0ull - NTL_END_PAD) return fail(c, NTL_EINVAL, "masked batch longer than 2^32 positions");
+    (void)hipSetDevice(c->device);
+    std::unique_ptr<ntl_batch> b = batch_new(c, n, total, total);
+    b->seq_len.resize(n);
+    for (uint64_t i = 0; i < n; i++) b->seq_len[i] = src->seq_len[src_seq[i]];
+    int rc;
+    DevBuf d_seq, d_lo, d_hi, d_first, d_stats;
+    if ((rc = b->packed.alloc(c, b->nwords_packed * 4)) || (rc = b->seq_base.alloc(c, (n + 1) * 8)) ||
+        (rc = b->seq_run_first.alloc(c, (n + 1) * 4)) || (rc = d_seq.alloc(c, (n + 1) * 4)) || (rc = d_lo.alloc(c, (n + 1) * 4)) ||
+        (rc = d_hi.alloc(c, (n + 1) * 4)) || (rc = d_first.alloc(c, (n + 1) * 4)) || (rc = d_stats.alloc(c, 16)))
+        return rc;
+    if (src->ready) HIPCHK(c, hipStreamWaitEvent(c->stream, src->ready, 0));
+    MaskArgs A;
+    A.src_packed = src->packed.as<uint32_t>(); A.src_seq_base = src->seq_base.as<uint64_t>();
+    A.src_seq_run_first = src->seq_run_first.as<uint32_t>(); A.src_run_start = src->run_start.as<uint32_t>();
+    A.src_run_len = src->run_len.as<uint32_t>(); A.n_src = (uint32_t)src->nseq;
+    A.src_seq = d_seq.as<uint32_t>(); A.keep_lo = d_lo.as<uint32_t>(); A.keep_hi = d_hi.as<uint32_t>(); A.n = n;
+    A.dst_packed = b->packed.as<uint32_t>(); A.dst_seq_base = b->seq_base.as<uint64_t>();
+    A.cnt = b->seq_run_first.as<uint32_t>(); A.first = d_first.as<uint32_t>(); A.dst_seq_run_first = b->seq_run_first.as<uint32_t>();
+    A.dst_run_start = nullptr; A.dst_run_len = nullptr; A.stats = d_stats.as<unsigned long long>();
+    const unsigned g_lane = (unsigned)((n + MASK_NT - 1) / MASK_NT), g_wave = (unsigned)((n + MASK_NT / 64 - 1) / (MASK_NT / 64));
+    unsigned long long stats[2] = {0, 0};
+    {
+        ProfSpan span(c, "batch_mask");
+        HIPCHK(c, hipMemcpyAsync(b->seq_base.p, seq_base.data(), (n + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if ((rc = batch_upload_seq_len(c, b.get()))) return rc;
+        HIPCHK(c, hipMemsetAsync(b->packed.p, 0, b->nwords_packed * 4, c->stream));
+        HIPCHK(c, hipMemsetAsync(b->seq_run_first.p, 0, (n + 1) * 4, c->stream)); /* counts; scanned in place */
+        HIPCHK(c, hipMemsetAsync(d_stats.p, 0, 16, c->stream));
+        if (n) {
+            HIPCHK(c, hipMemcpyAsync(d_seq.p, src_seq, n * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d_lo.p, keep_lo, n * 4, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(d_hi.p, keep_hi, n * 4, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(nmask_count_kernel, dim3(g_lane), dim3(MASK_NT), 0, c->stream, A);
+            hipLaunchKernelGGL(nmask_copy_kernel, dim3(g_wave), dim3(MASK_NT), 0, c->stream, A);
+            HIPCHK(c, hipGetLastError());
+        }
+        if ((rc = device_scan(c, b->seq_run_first.as<uint32_t>(), b->seq_run_first.as<uint32_t>(), n, nullptr))) return rc;
+        HIPCHK(c, hipMemcpyAsync(stats, d_stats.p, 16, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* the run count: the size of the run tables */
+    if (stats[0] >= 0xFFFFFFF0ull) return fail(c, NTL_EINVAL, "too many ACGT runs in one batch");
+    b->nruns = stats[0];
+    b->any_multi = stats[1] != 0;
+    if ((rc = b->run_start.alloc(c, (b->nruns + 1) * 4)) || (rc = b->run_len.alloc(c, (b->nruns + 1) * 4))) return rc;
+    if (b->nruns) {
+        ProfSpan span(c, "batch_mask");
+        A.dst_run_start = b->run_start.as<uint32_t>(); A.dst_run_len = b->run_len.as<uint32_t>();
+        hipLaunchKernelGGL(nmask_fill_kernel, dim3(g_lane), dim3(MASK_NT), 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream)); /* the temporaries go back to the block cache; the caller's arrays are free again */
+    *out = b.release();
+    return NTL_OK;
+}
+
+/* ntl_batch_download for any batch: upper-case ASCII with N wherever no run covers a base */
+extern "C" int ntl_batch_download_n(const ntl_batch *b, char *seqs, uint64_t *off)
+{
+    if (!b || (!seqs && b->bases) || !off) return NTL_EINVAL;
+    ntl_ctx *c = b->c;
+    (void)hipSetDevice(c->device);
+    uint64_t t = 0;
+    for (uint64_t i = 0; i < b->nseq; i++) { off[i] = t; t += b->seq_len[i]; }
+    off[b->nseq] = t;
+    if (t == 0) return NTL_OK;
+    DevBuf tmp, d_off;
+    int rc;
+    if ((rc = tmp.alloc(c, t + 16)) || (rc = d_off.alloc(c, (b->nseq + 1) * 8))) return rc;
+    if (b->ready) HIPCHK(c, hipStreamWaitEvent(c->stream, b->ready, 0));
+    HIPCHK(c, hipMemsetAsync(tmp.p, 'N', t, c->stream));
+    HIPCHK(c, hipMemcpyAsync(d_off.p, off, (b->nseq + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (b->nruns) {
+        hipLaunchKernelGGL(unpack_runs_kernel, dim3((unsigned)((b->nruns + MASK_NT / 64 - 1) / (MASK_NT / 64))), dim3(MASK_NT), 0, c->stream,
+                           (const uint32_t *)b->packed.as<uint32_t>(), (const uint64_t *)b->seq_base.as<uint64_t>(),
+                           (const uint32_t *)b->seq_run_first.as<uint32_t>(), (uint32_t)b->nseq, (const uint32_t *)b->run_start.as<uint32_t>(),
+                           (const uint32_t *)b->run_len.as<uint32_t>(), (uint64_t)b->nruns, (const uint64_t *)d_off.as<uint64_t>(),
+                           tmp.as<uint8_t>());
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(seqs, tmp.p, t, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
     return NTL_OK;
 }
 

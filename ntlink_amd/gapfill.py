@@ -35,6 +35,14 @@ device pass per block (Device.gap_select, ntl_gap_select, csrc/gap_select_kernel
 read) and nothing else, and the host keeps per pair the running best: anchor sum descending, then read id descending as a string.
 ``choose_gap_reads_restated`` is the three reference functions restated over formats.parse_verbose; the tests and
 tools/gapmap_bench.py compare against it, nothing falls back to it.
+
+Between the two the reference writes and reads two temporary FASTA files (get_gap_fill_reads :264-273, print_masked_sequences :346-389):
+per gap the whole source scaffold, the whole target scaffold and the whole read, N-masked but for the scaffold end beside the gap and
+the read piece between its cuts.  ``get_gap_fill_reads`` / ``resident_scaffolds`` keep the chosen reads and the scaffolds on the device
+instead, ``mask_ranges`` says what every record keeps, and ``gap_cuts_resident`` / ``map_long_reads_resident`` make the masked
+full-length records there (Device.batch_mask, ntl_batch_mask, csrc/mask_kernels.h) and go on as the file form does: the same GapCuts,
+the same fields in ``pairs`` and ``scaffolds``, the two files never written.  ``print_masked_sequences`` is the reference's function
+restated over bytes for whoever wants the files; nothing falls back to it.
 """
 import collections
 import itertools
@@ -201,6 +209,15 @@ def _is_minus(record_id):
     return sign == "-"
 
 
+def _cut_device(dev, sb, rb, ctg_len, read_len, src_minus, tgt_minus, k, w, args):
+    """sketch, sketch, map_grouped, gap_cuts over the resident batches sb (two records per gap) and rb (one per gap)"""
+    n = len(read_len)
+    with dev.sketch(sb, k, w) as ssk, dev.sketch(rb, k, w) as rsk, \
+            dev.map_grouped(ssk, ctg_len, 2 * np.arange(n + 1, dtype=np.uint32), rsk, read_len, np.arange(n + 1, dtype=np.uint32),
+                            k=int(args.k), z=int(args.z), x=float(args.x), sensitive=bool(args.sensitive)) as res:
+        return res.gap_cuts(src_minus, tgt_minus, int(args.k))
+
+
 def _cut_batch(dev, scaffolds, reads, k, w, args, name_of):
     """one device pass over len(reads) gaps: sketch, sketch, map_grouped, gap_cuts; nothing but the cut records comes back"""
     n = len(reads)
@@ -208,11 +225,8 @@ def _cut_batch(dev, scaffolds, reads, k, w, args, name_of):
     tgt_minus = np.fromiter((_is_minus(scaffolds[2 * g + 1][0]) for g in range(n)), np.uint8, n)
     ctg_len = np.fromiter((len(seq) for _id, seq in scaffolds), np.uint32, 2 * n)
     read_len = np.fromiter((len(seq) for _id, seq in reads), np.uint32, n)
-    with dev.batch([bytes(seq) for _id, seq in scaffolds]) as sb, dev.batch([bytes(seq) for _id, seq in reads]) as rb, \
-            dev.sketch(sb, k, w) as ssk, dev.sketch(rb, k, w) as rsk, \
-            dev.map_grouped(ssk, ctg_len, 2 * np.arange(n + 1, dtype=np.uint32), rsk, read_len, np.arange(n + 1, dtype=np.uint32),
-                            k=int(args.k), z=int(args.z), x=float(args.x), sensitive=bool(args.sensitive)) as res:
-        cuts = res.gap_cuts(src_minus, tgt_minus, int(args.k))
+    with dev.batch([bytes(seq) for _id, seq in scaffolds]) as sb, dev.batch([bytes(seq) for _id, seq in reads]) as rb:
+        cuts = _cut_device(dev, sb, rb, ctg_len, read_len, src_minus, tgt_minus, k, w, args)
     for g in range(n):  # one contig in the reference's dict: never two accepted contigs (see the module's text)
         if name_of(scaffolds[2 * g][0]) == name_of(scaffolds[2 * g + 1][0]):
             cuts[g] = (capi.NTL_GAP_NOT_TWO, 0, 0, 0, 0, 0, 0, 0)
@@ -260,6 +274,28 @@ def _fallback_old_anchor_cuts(pair, scaffolds, source_name, src_minus, target_na
         scaffolds[target_name].three_prime_cut = pair.target_ctg_cut
 
 
+def _apply_cut(pair, scaffolds, args, source_name, src_minus, target_name, tgt_minus, cut):
+    """what :443-489 write for one gap: `cut` is its capi.GAP_CUT_DT record as a tuple"""
+    status, src_pos, src_read_cut, src_end_cut, tgt_pos, tgt_read_cut, tgt_end_cut, _ori = cut
+    if status:  # not two accepted contigs, mixed strands or inconsistent positions (:443-463)
+        if args.stringent:
+            pair.source_read_cut = None
+            pair.target_read_cut = None
+        else:
+            _fallback_old_anchor_cuts(pair, scaffolds, source_name, src_minus, target_name, tgt_minus)
+        return
+    pair.source_ctg_cut, pair.source_read_cut = src_pos, src_read_cut
+    if not src_minus:
+        scaffolds[source_name].three_prime_cut = src_end_cut
+    else:
+        scaffolds[source_name].five_prime_cut = src_end_cut
+    pair.target_ctg_cut, pair.target_read_cut = tgt_pos, tgt_read_cut
+    if not tgt_minus:
+        scaffolds[target_name].five_prime_cut = tgt_end_cut
+    else:
+        scaffolds[target_name].three_prime_cut = tgt_end_cut
+
+
 def map_long_reads(pairs, scaffolds, args, dev=None, batch_bases=BATCH_BASES):
     """The reference's map_long_reads (:412-489): reads ``args.o + ".scaffolds.masked_temp.fa"`` / ``".reads.masked_temp.fa"``, uses
     ``args.k .w .z .x .sensitive .stringent`` and writes ``pairs[(source, target)].source_ctg_cut / source_read_cut / target_ctg_cut /
@@ -268,32 +304,13 @@ def map_long_reads(pairs, scaffolds, args, dev=None, batch_bases=BATCH_BASES):
     got = gap_cuts(args.o + ".scaffolds.masked_temp.fa", args.o + ".reads.masked_temp.fa", int(args.k), int(args.w), args, dev=dev,
                    batch_bases=batch_bases)
     for g, cut in enumerate(got.cuts.tolist()):
-        status, src_pos, src_read_cut, src_end_cut, tgt_pos, tgt_read_cut, tgt_end_cut, _ori = cut
         _, source, target = _READ_HEADER.search(got.read_ids[g]).groups()
         source_id, label = _SCAFFOLD_HEADER.search(got.scaffold_ids[2 * g]).groups()
         assert source_id == source and label == "source"
         target_id, label = _SCAFFOLD_HEADER.search(got.scaffold_ids[2 * g + 1]).groups()
         assert target_id == target and label == "target"
-        source_name, target_name = source_id.strip("+-"), target_id.strip("+-")
-        src_minus, tgt_minus = bool(got.src_minus[g]), bool(got.tgt_minus[g])
-        pair = pairs[(source, target)]
-        if status:  # not two accepted contigs, mixed strands or inconsistent positions (:443-463)
-            if args.stringent:
-                pair.source_read_cut = None
-                pair.target_read_cut = None
-            else:
-                _fallback_old_anchor_cuts(pair, scaffolds, source_name, src_minus, target_name, tgt_minus)
-            continue
-        pair.source_ctg_cut, pair.source_read_cut = src_pos, src_read_cut
-        if not src_minus:
-            scaffolds[source_name].three_prime_cut = src_end_cut
-        else:
-            scaffolds[source_name].five_prime_cut = src_end_cut
-        pair.target_ctg_cut, pair.target_read_cut = tgt_pos, tgt_read_cut
-        if not tgt_minus:
-            scaffolds[target_name].five_prime_cut = tgt_end_cut
-        else:
-            scaffolds[target_name].three_prime_cut = tgt_end_cut
+        _apply_cut(pairs[(source, target)], scaffolds, args, source_id.strip("+-"), bool(got.src_minus[g]), target_id.strip("+-"),
+                   bool(got.tgt_minus[g]), cut)
 
 
 def _records_of(path, batch_bases):
@@ -309,6 +326,191 @@ def map_gap_reads(scaffolds_fasta, reads_fasta, k, w, args, dev=None, with_minim
     A scaffold count other than twice the read count raises ValueError."""
     return _map_records(_records_of(scaffolds_fasta, batch_bases), _records_of(reads_fasta, batch_bases), k, w, args, dev,
                         with_minimizers, name_of, batch_bases)
+
+
+# ---------------------------------------------------------------- without the two temporary files (bin/ntlink_patch_gaps.py:264-273, 346-389)
+
+class Resident:
+    """Records resident on the device: ``ids``, ``lengths`` (u32), ``number`` (id -> record number) and ``batch`` (capi.Batch).  With
+    keep_ascii also the bytes as they were read, case and IUPAC codes included (``buf``, ``offsets``; ``resident[id]`` is one
+    record's).  Close it, or use it as a context manager, to free the batch."""
+
+    def __init__(self, ids, lengths, batch, buf=None, offsets=None):
+        self.ids, self.lengths, self.batch, self.buf, self.offsets = list(ids), np.ascontiguousarray(lengths, np.uint32), batch, buf, offsets
+        self.number = {rid: i for i, rid in enumerate(self.ids)}
+        if len(self.number) != len(self.ids):
+            raise ValueError("two records with the same id")
+
+    def __len__(self):
+        return len(self.ids)
+
+    def __contains__(self, rid):
+        return rid in self.number
+
+    def __getitem__(self, rid):
+        if self.buf is None:
+            raise ValueError("the records' bytes were not kept (keep_ascii=True keeps them)")
+        i = self.number[rid]
+        return bytes(self.buf[int(self.offsets[i]):int(self.offsets[i + 1])])
+
+    def length_of(self):
+        return dict(zip(self.ids, self.lengths.tolist()))
+
+    def close(self):
+        if self.batch is not None:
+            self.batch.close()
+            self.batch = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+
+def _resident(dev, ids, seqs, keep_ascii):
+    lens = np.fromiter((len(s) for s in seqs), np.uint64, len(seqs))
+    offsets = np.zeros(len(seqs) + 1, np.uint64)
+    np.cumsum(lens, out=offsets[1:])
+    buf = np.frombuffer(b"".join(seqs), np.uint8)
+    batch = dev.batch(buf, offsets)
+    return Resident(ids, lens, batch, buf if keep_ascii else None, offsets if keep_ascii else None)
+
+
+def get_gap_fill_reads(reads_filename_list, pairs, args=None, dev=None, keep_ascii=False, max_bases=BATCH_BASES):
+    """get_gap_fill_reads (:264-273): goes through the read files (FASTA / FASTQ, gzip or not) and keeps the chosen reads of `pairs`
+    only -- as ONE resident batch instead of a dict of strings.  A later record with the same id replaces an earlier one, as the
+    reference's dict does (and keeps the earlier one's place).  -> Resident.  `args` is not read (the reference takes its thread
+    count from it)."""
+    dev = dev or anchor._default_device()
+    wanted = {p.chosen_read for p in pairs.values() if p.chosen_read is not None}
+    kept = {}
+    for ss in seqio.load(list(reads_filename_list), max_bases=max_bases):
+        off = ss.offsets.tolist()
+        for i, name in enumerate(ss.names):
+            if name in wanted:
+                kept[name] = bytes(ss.buf[off[i]:off[i + 1]])
+    return _resident(dev, list(kept), list(kept.values()), keep_ascii)
+
+
+def resident_scaffolds(path_or_records, dev=None, keep_ascii=False):
+    """The scaffolds of ``args.s`` as one resident batch: a FASTA path, or records [(id, sequence as bytes or str)].  -> Resident.
+    One batch holds up to 2^32 - 4112 bases."""
+    dev = dev or anchor._default_device()
+    if isinstance(path_or_records, str):
+        ss = seqio.load_all([path_or_records])
+        return Resident(ss.names.tolist(), ss.lengths, dev.batch(ss.buf, ss.offsets), ss.buf if keep_ascii else None,
+                        ss.offsets if keep_ascii else None)
+    recs = [(rid, seq.encode() if isinstance(seq, str) else bytes(seq)) for rid, seq in path_or_records]
+    return _resident(dev, [rid for rid, _seq in recs], [seq for _rid, seq in recs], keep_ascii)
+
+
+MaskRanges = collections.namedtuple("MaskRanges", "keys scaffold_names scaffold_lo scaffold_hi read_ids read_lo read_hi src_minus tgt_minus")
+
+
+def mask_ranges(pairs, scaffold_lengths, read_lengths):
+    """What print_masked_sequences keeps of every record it writes (:351-386), as half-open ranges.  Pairs in dict order, pairs
+    without a chosen read skipped.  -> MaskRanges: per gap g its key (source, target), scaffold_names[2g], [2g+1] and the ranges
+    scaffold_lo/hi[2g], [2g+1] (source +: [cut, len), source -: [0, cut), target +: [0, cut), target -: [cut, len)), the read's id
+    and its range [min, max) of the two read cuts, and the two signs (1: '-').  scaffold_lengths: name -> length; read_lengths:
+    read id -> length.  ValueError for a node that does not end in + or - (the reference's) and for a cut beyond its sequence, where
+    Python's slices would silently make the record longer."""
+    keys, names, read_ids, slo, shi, rlo, rhi, sm, tm = [], [], [], [], [], [], [], [], []
+    for (source, target), info in pairs.items():
+        if info.chosen_read is None:
+            continue
+        for node, cut, is_source in ((source, info.source_ctg_cut, True), (target, info.target_ctg_cut, False)):
+            if node[-1:] not in ("+", "-"):
+                raise ValueError(f"{node[-1:]} must be + or -")
+            name, minus = node.strip("+-"), node[-1] == "-"
+            length = int(scaffold_lengths[name])
+            if not 0 <= cut <= length:
+                raise ValueError(f"pair {source} {target}: cut {cut} outside {name}'s {length} bases")
+            tail = minus != is_source  # source +, target -: the end behind the cut is kept
+            slo.append(cut if tail else 0)
+            shi.append(length if tail else cut)
+            names.append(name)
+            (sm if is_source else tm).append(minus)
+        a, b = sorted((info.source_read_cut, info.target_read_cut))
+        length = int(read_lengths[info.chosen_read])
+        if not 0 <= a <= b <= length:
+            raise ValueError(f"pair {source} {target}: read cuts {a}, {b} outside {info.chosen_read}'s {length} bases")
+        keys.append((source, target)); read_ids.append(info.chosen_read); rlo.append(a); rhi.append(b)
+    u32 = lambda v: np.array(v, np.uint32)
+    return MaskRanges(keys, names, u32(slo), u32(shi), read_ids, u32(rlo), u32(rhi), np.array(sm, np.uint8), np.array(tm, np.uint8))
+
+
+def gap_cuts_resident(pairs, scaffolds, reads, k, w, args, dev=None, batch_bases=BATCH_BASES):
+    """gap_cuts without the two files: the same GapCuts as gap_cuts over what print_masked_sequences would write for `pairs`.
+    scaffolds, reads: Resident (resident_scaffolds, get_gap_fill_reads).  Gaps are batched as the file form batches them -- by the full
+    lengths of their three records, a gap never split -- and per batch two Device.batch_mask calls make the masked records on the
+    device (csrc/mask_kernels.h); then sketch, sketch, map_grouped, gap_cuts as ever."""
+    dev = dev or anchor._default_device()
+    r = mask_ranges(pairs, scaffolds.length_of(), reads.length_of())
+    n = len(r.keys)
+    snum = np.fromiter((scaffolds.number[name] for name in r.scaffold_names), np.uint32, 2 * n)
+    rnum = np.fromiter((reads.number[rid] for rid in r.read_ids), np.uint32, n)
+    ctg_len, read_len = scaffolds.lengths[snum], reads.lengths[rnum]
+    per_gap = (read_len.astype(np.int64) + ctg_len[0::2] + ctg_len[1::2]).tolist()
+    bounds, bases = [0], 0
+    for g, add in enumerate(per_gap):
+        if g > bounds[-1] and bases + add > batch_bases:
+            bounds.append(g)
+            bases = 0
+        bases += add
+    bounds.append(n)
+    cuts = np.zeros(n, capi.GAP_CUT_DT)
+    for a, b in zip(bounds, bounds[1:]):
+        if a == b:
+            continue
+        with dev.batch_mask(scaffolds.batch, snum[2 * a:2 * b], r.scaffold_lo[2 * a:2 * b], r.scaffold_hi[2 * a:2 * b]) as sb, \
+                dev.batch_mask(reads.batch, rnum[a:b], r.read_lo[a:b], r.read_hi[a:b]) as rb:
+            cuts[a:b] = _cut_device(dev, sb, rb, ctg_len[2 * a:2 * b], read_len[a:b], r.src_minus[a:b], r.tgt_minus[a:b], k, w, args)
+    for g in range(n):  # one contig in the reference's dict: never two accepted contigs (see the module's text)
+        if r.scaffold_names[2 * g] == r.scaffold_names[2 * g + 1]:
+            cuts[g] = (capi.NTL_GAP_NOT_TWO, 0, 0, 0, 0, 0, 0, 0)
+    read_ids = [f"{rid}__{source}__{target}" for rid, (source, target) in zip(r.read_ids, r.keys)]
+    scaffold_ids = [sid for source, target in r.keys for sid in (source + "_source", target + "_target")]
+    return GapCuts(cuts, read_ids, scaffold_ids, r.src_minus, r.tgt_minus)
+
+
+def map_long_reads_resident(pairs, sequences, scaffolds, reads, args, dev=None, batch_bases=BATCH_BASES):
+    """map_long_reads without the two files: writes into ``pairs`` and ``sequences`` (name -> object with ``five_prime_cut``,
+    ``three_prime_cut``) exactly what map_long_reads writes after print_masked_sequences.  scaffolds, reads: Resident.  Source, target
+    and the signs come from the keys of ``pairs``, not from record headers."""
+    got = gap_cuts_resident(pairs, scaffolds, reads, int(args.k), int(args.w), args, dev=dev, batch_bases=batch_bases)
+    keys = [key for key, info in pairs.items() if info.chosen_read is not None]
+    for g, (cut, (source, target)) in enumerate(zip(got.cuts.tolist(), keys)):
+        _apply_cut(pairs[(source, target)], sequences, args, source.strip("+-"), bool(got.src_minus[g]), target.strip("+-"),
+                   bool(got.tgt_minus[g]), cut)
+
+
+def print_masked_sequences(scaffolds, reads, pairs, args):
+    """print_masked_sequences (:346-389) restated over bytes: writes ``args.o + ".scaffolds.masked_temp.fa"`` and
+    ``".reads.masked_temp.fa"``, byte for byte the reference's.  scaffolds: name -> sequence, or -> object with ``.seq``; reads: id ->
+    sequence (str or bytes; a Resident made with keep_ascii serves as either).  For whoever wants the two files and for
+    tools/gapmap_bench.py's file leg; nothing falls back to it."""
+    def seq_of(rec):
+        rec = getattr(rec, "seq", rec)
+        return rec.encode() if isinstance(rec, str) else rec
+
+    with open(args.o + ".scaffolds.masked_temp.fa", "wb") as out_scaffolds, open(args.o + ".reads.masked_temp.fa", "wb") as out_reads:
+        for (source, target), info in pairs.items():
+            if info.chosen_read is None:
+                continue
+            for node, cut, label, tail_on in ((source, info.source_ctg_cut, b"_source", "+"), (target, info.target_ctg_cut, b"_target", "-")):
+                if node[-1:] not in ("+", "-"):
+                    raise ValueError(f"{node[-1:]} must be + or -")
+                seq = seq_of(scaffolds[node.strip("+-")])
+                if node[-1] == tail_on:
+                    body = b"N" * cut + seq[cut:]
+                else:
+                    body = seq[:cut] + b"N" * (len(seq) - cut)
+                out_scaffolds.write(b">" + node.encode() + label + b"\n" + body + b"\n")
+            start, end = sorted((info.source_read_cut, info.target_read_cut))
+            seq = seq_of(reads[info.chosen_read])
+            out_reads.write(b">" + f"{info.chosen_read}__{source}__{target}".encode() + b"\n" + b"N" * start + seq[start:end] +
+                            b"N" * (len(seq) - end) + b"\n")
 
 
 # ---------------------------------------------------------------- the read of every gap (bin/ntlink_patch_gaps.py:94-111, 149-261, 311-342)

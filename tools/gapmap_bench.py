@@ -18,7 +18,14 @@ For G synthetic gaps (two scaffold ends of 300 .. 3000 bases, one read piece acr
             Python; both must leave the same fields in every pair), the three kernels of ntl_gap_select alone (ntl_prof_get
             "gap_select": assess, count, scan with its host wait, fill) beside the bytes the block uploads, and the reader alone in
             GB/s of text.
-Prints one JSON line per G (and one per G for --cuts / --select)."""
+  mask      (--mask) from the chosen reads to the final cuts, with and without the two temporary files: a chain of G + 1 scaffolds of
+            --scaffold-len bases (50 kb: 2 G records of that length are written, 0.2 GB at 2 000 gaps and 2 GB at 20 000), per gap a read
+            of 1 .. 6 kb whose middle spans the gap with 5 % errors, random signs; best of --repeat, alternating:
+            (a) gapfill.print_masked_sequences (timed as `write_s`) and gapfill.map_long_reads over the two files (`read_s`),
+            (b) gapfill.map_long_reads_resident over the resident scaffolds and reads (`resident_s`; making the two resident batches
+            once is `setup_s`), with the batch_mask kernels' share (ntl_prof_get "batch_mask") from one more run.  Both must leave the
+            same fields in every pair and scaffold.
+Prints one JSON line per G (and one per G for --cuts / --select / --mask)."""
 import argparse
 import json
 import sys
@@ -253,6 +260,81 @@ def select_leg(dev, G, repeat):
                           "kernels_GBps_of_upload": up / kernel_ms / 1e6 if kernel_ms else None, "device": dev.name}), flush=True)
 
 
+def mask_leg(dev, G, repeat, scaffold_len):
+    rng = np.random.default_rng(G)
+    comp = bytes.maketrans(b"ACGT", b"TGCA")
+    blob = ACGT[rng.integers(0, 4, (G + 1) * scaffold_len, dtype=np.uint8)].tobytes()
+    seqs = {f"c{i}": blob[i * scaffold_len:(i + 1) * scaffold_len] for i in range(G + 1)}
+    del blob
+    reads, spec = {}, []
+    for g in range(G):
+        s, t = "+-"[int(rng.integers(0, 2))], "+-"[int(rng.integers(0, 2))]
+        rs, rt = int(rng.integers(250, 900)), int(rng.integers(250, 900))
+        src, tgt = seqs[f"c{g}"], seqs[f"c{g + 1}"]
+        end = src[-rs:] if s == "+" else src[:rs].translate(comp)[::-1]
+        start = tgt[:rt] if t == "+" else tgt[-rt:].translate(comp)[::-1]
+        piece = np.frombuffer(end + ACGT[rng.integers(0, 4, int(rng.integers(50, 400)))].tobytes() + start, np.uint8).copy()
+        hit = rng.random(len(piece)) < 0.05
+        piece[hit] = ACGT[rng.integers(0, 4, int(hit.sum()))]
+        pre, post = (ACGT[rng.integers(0, 4, int(rng.integers(0, 2500)))].tobytes() for _ in range(2))
+        read = pre + piece.tobytes() + post
+        cuts = (len(pre), len(pre) + len(piece))
+        if g & 1:  # every other read against the path
+            read, cuts = read.translate(comp)[::-1], (len(read) - cuts[0], len(read) - cuts[1])
+        reads[f"r{g}"] = read
+        keep_s, keep_t = int(rng.integers(rs, 3001)), int(rng.integers(rt, 3001))
+        spec.append((f"c{g}{s}", f"c{g + 1}{t}", scaffold_len - keep_s if s == "+" else keep_s, cuts[0],
+                     keep_t if t == "+" else scaffold_len - keep_t, cuts[1]))
+
+    def fresh():
+        pairs = {}
+        for g, (source, target, sc, sr, tc, tr) in enumerate(spec):
+            p = gapfill.PairInfo(100)
+            p.chosen_read, p.source_ctg_cut, p.source_read_cut, p.target_ctg_cut, p.target_read_cut = f"r{g}", sc, sr, tc, tr
+            pairs[(source, target)] = p
+        return pairs, {name: types.SimpleNamespace(five_prime_cut=0, three_prime_cut=scaffold_len) for name in seqs}
+
+    state = lambda pairs, scaf: ([vars(p) for p in pairs.values()], {n: vars(x) for n, x in scaf.items()})
+    t0 = time.perf_counter()
+    res_s, res_r = gapfill.resident_scaffolds(seqs.items(), dev=dev), gapfill.resident_scaffolds(reads.items(), dev=dev)
+    dev.sync()
+    t_setup = time.perf_counter() - t0
+    t_write, t_read, t_res, states = [], [], [], []
+    with tempfile.TemporaryDirectory() as tmp:
+        args = argparse.Namespace(o=os.path.join(tmp, "g"), k=K, w=W, z=1000, x=0.0, sensitive=False, stringent=False)
+        gapfill.map_long_reads_resident(*fresh(), res_s, res_r, args, dev=dev)  # warm-up
+        for _ in range(repeat):
+            pairs, scaf = fresh()
+            t0 = time.perf_counter()
+            gapfill.print_masked_sequences(seqs, reads, pairs, args)
+            t1 = time.perf_counter()
+            gapfill.map_long_reads(pairs, scaf, args, dev=dev)
+            t2 = time.perf_counter()
+            t_write.append(t1 - t0); t_read.append(t2 - t1)
+            states.append(state(pairs, scaf))
+            pairs, scaf = fresh()
+            t0 = time.perf_counter()
+            gapfill.map_long_reads_resident(pairs, scaf, res_s, res_r, args, dev=dev)
+            t_res.append(time.perf_counter() - t0)
+            states.append(state(pairs, scaf))
+        text_bytes = os.path.getsize(args.o + ".scaffolds.masked_temp.fa") + os.path.getsize(args.o + ".reads.masked_temp.fa")
+        assert all(st == states[0] for st in states), "the two ways leave different cuts"
+        dev.set_pipeline(False)
+        dev.prof_enable(True)
+        dev.prof_reset()
+        gapfill.map_long_reads_resident(*fresh(), res_s, res_r, args, dev=dev)
+        dev.sync()
+        ms, launches = dev.prof_get("batch_mask")
+        dev.prof_enable(False)
+        dev.set_pipeline(True)
+    res_s.close(); res_r.close()
+    new_cuts = sum(not p["old_anchor_used"] for p in states[0][0])
+    print(json.dumps({"leg": "mask", "gaps": G, "scaffold_len": scaffold_len, "text_bytes": text_bytes, "write_s": min(t_write), "write_s_all": t_write,
+                      "read_s": min(t_read), "read_s_all": t_read, "resident_s": min(t_res), "resident_s_all": t_res, "setup_s": t_setup,
+                      "read_over_resident": min(t_read) / min(t_res), "files_over_resident": (min(t_write) + min(t_read)) / min(t_res),
+                      "new_cuts": new_cuts, "batch_mask_ms": ms, "batch_mask_spans": launches, "device": dev.name}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gaps", type=int, nargs="+", default=[2000, 20000])
@@ -260,9 +342,16 @@ def main():
     ap.add_argument("--repeat", type=int, default=3)
     ap.add_argument("--cuts", action="store_true", help="the cuts leg alone: gapfill.map_long_reads beside map_gap_reads + the assess in Python")
     ap.add_argument("--select", action="store_true", help="the select leg alone: gapfill.choose_gap_reads beside the three reference functions in Python")
+    ap.add_argument("--mask", action="store_true", help="the mask leg alone: the two temporary files written and read beside gapfill.map_long_reads_resident")
+    ap.add_argument("--scaffold-len", type=int, default=50000, help="bases per scaffold of the mask leg")
     a = ap.parse_args()
     args = argparse.Namespace(k=K, z=1000, x=0.0, sensitive=False)
     dev = capi.Device(0)
+    if a.mask:
+        for G in a.gaps:
+            mask_leg(dev, G, a.repeat, a.scaffold_len)
+        dev.close()
+        return
     if a.select:
         for G in a.gaps:
             select_leg(dev, G, a.repeat)
