@@ -461,11 +461,13 @@ def check_overlap_random(dev, seed, nseq=40, max_len=30000, k=15, w=5):
             starts.append(a); ends.append(b)
         off[i + 1] = len(starts)
     with dev.batch(seqs) as b, dev.sketch(b, k, w) as sk:
-        m_off, h, p, _ = sk.download()
+        m_off, h, p, s = sk.download()
         with dev.overlap_filter(sk, off, np.array(starts, np.uint32), np.array(ends, np.uint32)) as kept:
-            g_off, gh, gp, _gs = kept.download()
+            g_off, gh, gp, gs = kept.download()
     e_off, eh, ep = oracle.overlap_filter(m_off, h, p, regions)
     assert np.array_equal(g_off, e_off) and np.array_equal(gh, eh) and np.array_equal(gp, ep)
+    from overlap_cases import kept_indices
+    assert np.array_equal(gs, s[kept_indices(m_off, h, p, e_off, eh, ep)]), "the strands of the kept records are the input's"
     assert 0 < len(eh) < len(h)
     return len(eh), len(h)
 

@@ -7,12 +7,17 @@ same checks.
   b. random reads: the device's candidate records, record for record, against gapfill.restated_candidates on the same file; and the end
      state of choose_gap_reads against choose_gap_reads_restated (the reference's assertion included)
   c. the reader's arrays against formats.parse_verbose on those files, and its four refusals with their line numbers
-  d. the refusals of the device call: a pair table more than half full, a read with a contig twice"""
+  d. the refusals of the device call: a pair table more than half full, a read with a contig twice
+  e. a pair table with chosen keys: 20 pairs of one home across the end of a table of 64 slots, 6 of another, exactly half full; reads of
+     present pairs, of their reverse complements, of absent pairs whose probes walk the cluster to the empty slot behind it, and one of
+     five mappings -- against restated_candidates record for record, the table itself against a linear-probe simulation"""
 import argparse
 import functools
 import gzip
+import itertools
 import json
 import os
+import re
 import types
 
 import numpy as np
@@ -326,6 +331,187 @@ def check_refusals(dev, tmp_path):
     dev.sync()
 
 
+# ---------------------------------------------------------------- e. a pair table of chosen keys
+
+GSEL_MULT = 0x9E3779B97F4A7C15
+E_SLOTS, E_CTG, E_CTG_LEN = 64, 40, 20000
+EMPTY_KEY = 0xFFFFFFFFFFFFFFFF
+
+
+def gsel_slot(key, n_slots):
+    """gsel_slot of csrc/gap_select_kernels.h: the slot a key's probe sequence starts at"""
+    return (((key * GSEL_MULT) & EMPTY_KEY) >> 32) & (n_slots - 1)
+
+
+def test_pair_table_source_literals():
+    """cluster_case picks its pairs by gsel_slot above.  If the kernel's or the host's rule changes, the chosen clusters quietly turn
+    into scattered keys: change the restatement with them."""
+    squeezed = lambda name: re.sub(r"\s+", " ", open(os.path.join(os.path.dirname(HERE), "ntlink_amd", "csrc", name)).read())
+    kernels, host = squeezed("gap_select_kernels.h"), squeezed("ntl_hip.hip")
+    assert "uint64_t gsel_slot(uint64_t key, uint64_t n_slots) { return ((key * 0x%Xull) >> 32) & (n_slots - 1ull); }" % GSEL_MULT in kernels
+    assert "uint64_t s = gsel_slot(key, A.n_slots);" in kernels and "s = (s + 1ull) & (A.n_slots - 1ull);" in kernels
+    assert "if (have == key) return A.pair_vals[s]; if (have == GSEL_EMPTY) return GSEL_NONE;" in kernels
+    assert "uint64_t s = gsel_slot(keys[i], n_slots); while (slot_keys[s] != GSEL_EMPTY) {" in host and "s = (s + 1) & (n_slots - 1);" in host
+    assert "#define GSEL_EMPTY 0x%Xull" % EMPTY_KEY in kernels
+    assert gsel_slot(0, 64) == 0 and gsel_slot(1, 64) == (GSEL_MULT >> 32) & 63 == 0x39 and gsel_slot(1 << 32, 1 << 32) == GSEL_MULT & 0xFFFFFFFF
+
+
+def _node_name(node):
+    return f"c{node >> 1}" + "+-"[node & 1]
+
+
+def _revcomp_key(key):
+    return (((key & 0xFFFFFFFF) ^ 1) << 32) | ((key >> 32) ^ 1)
+
+
+def probe_table(keys, n_slots):
+    """ntl_gap_pair_table in Python: (slot keys, slot values) of linear-probe inserts in the order of `keys`"""
+    sk, sv = [EMPTY_KEY] * n_slots, [0] * n_slots
+    for i, key in enumerate(keys):
+        s = gsel_slot(key, n_slots)
+        while sk[s] != EMPTY_KEY:
+            s = (s + 1) & (n_slots - 1)
+        sk[s], sv[s] = key, i
+    return sk, sv
+
+
+def first_empty(sk, s):
+    while sk[s] != EMPTY_KEY:
+        s = (s + 1) & (len(sk) - 1)
+    return s
+
+
+@functools.lru_cache(maxsize=None)
+def cluster_case(seed=11):
+    """(keys, verbose text, read kinds, an unused key): 40 contigs = 80 nodes, the 6240 keys of two nodes on different contigs
+    enumerated by their home in a table of 64 slots.  32 pairs, none the reverse complement of another: 20 of home 62 (slots 62, 63,
+    0 .. 17), 6 of home 30, one of home 3 (inside the cluster's run, which it lengthens to slot 18: the first empty slot behind it is 19), five of homes 40 .. 50.
+    Reads: one per pair; one per reverse complement of every third pair; three each of absent pairs (absent as reverse complement
+    too) of the homes 62, 63, 0, 17 -- inside the cluster, to be walked to slot 19 -- and 50; one of five mappings whose ten
+    combinations hold present pairs, absent ones of a home inside the cluster and absent ones of an empty home."""
+    rng = np.random.default_rng(seed)
+    by_home = {}
+    for s, t in itertools.product(range(2 * E_CTG), repeat=2):
+        if s >> 1 != t >> 1:
+            by_home.setdefault(gsel_slot((s << 32) | t, E_SLOTS), []).append((s << 32) | t)
+    assert sum(len(v) for v in by_home.values()) == 6240 and len(by_home) == E_SLOTS
+    keys = []
+
+    def take(home, n):
+        got = []
+        for i in rng.permutation(len(by_home[home])):
+            key = by_home[home][i]
+            if key not in keys + got and _revcomp_key(key) not in keys + got:
+                got.append(key)
+                if len(got) == n:
+                    return got
+        raise AssertionError(home)
+
+    for home, n in ((62, 20), (30, 6), (3, 1), (40, 1), (41, 1), (45, 1), (50, 2)):
+        keys += take(home, n)
+    keys = [keys[i] for i in rng.permutation(len(keys))]
+    assert len(keys) == E_SLOTS // 2 == len(set(keys))
+    present = set(keys)
+    absent = lambda key: key not in present and _revcomp_key(key) not in present
+    sk, _sv = probe_table(keys, E_SLOTS)
+    occupied = {s for s in range(E_SLOTS) if sk[s] != EMPTY_KEY}
+    assert occupied == {62, 63} | set(range(19)) | set(range(30, 36)) | {40, 41, 45, 50, 51}
+    assert sorted(gsel_slot(sk[s], E_SLOTS) for s in [62, 63] + list(range(19))) == [3] + [62] * 20  # whichever of them lies where
+    assert all(first_empty(sk, h) == 19 for h in (62, 63, 0, 17))
+
+    reads = []  # (kind, [nodes in read order])
+    for key in keys:
+        reads.append(("present", [key >> 32, key & 0xFFFFFFFF]))
+    for key in keys[::3]:
+        rc = _revcomp_key(key)
+        reads.append(("revcomp", [rc >> 32, rc & 0xFFFFFFFF]))
+    for home in (62, 63, 0, 17, 50):
+        got = [key for key in (by_home[home][i] for i in rng.permutation(len(by_home[home]))) if absent(key)][:3]
+        assert len(got) == 3
+        reads += [("absent", [key >> 32, key & 0xFFFFFFFF]) for key in got]
+    unused = next(key for key in by_home[20] if absent(key))
+    in_cluster = lambda key: gsel_slot(key, E_SLOTS) in occupied
+    while True:  # five nodes on five contigs, two of them a pair of the cluster and two more a pair of home 30
+        a, b = keys[int(rng.integers(0, len(keys)))], keys[int(rng.integers(0, len(keys)))]
+        if gsel_slot(a, E_SLOTS) != 62 or gsel_slot(b, E_SLOTS) != 30:
+            continue
+        nodes = [a >> 32, b >> 32, int(rng.integers(0, 2 * E_CTG)), a & 0xFFFFFFFF, b & 0xFFFFFFFF]
+        if len({n >> 1 for n in nodes}) < 5:
+            continue
+        tried = [(s << 32) | t for s, t in itertools.combinations(nodes, 2)]
+        found = [key for key in tried if key in present or _revcomp_key(key) in present]
+        missed = [key for key in tried if key not in present]
+        if len(found) >= 2 and sum(1 for key in missed if in_cluster(key)) >= 2 and sum(1 for key in missed if not in_cluster(key)) >= 2:
+            reads.append(("five", nodes))
+            break
+    rows, kinds = [], []
+    for r, (kind, nodes) in enumerate(reads):
+        kinds.append(kind)
+        rpos = int(rng.integers(0, 3000))
+        for node in nodes:
+            toks, last = _hits(rng, (1, 2, 3, 65)[int(rng.integers(0, 4))], E_CTG_LEN, rpos, not node & 1, 0)
+            rows.append(f"read{r}\tc{node >> 1}\t{int(rng.integers(1, 200))}\t{toks}")
+            rpos = last + int(rng.integers(50, 4000))
+    return keys, "".join(row + "\n" for row in rows), kinds, unused
+
+
+def check_pair_clusters(dev, tmp_path):
+    keys, verbose, kinds, unused = cluster_case()
+    vp = _write(tmp_path, "e.verbose_mapping.tsv", verbose)
+    ctg_names = [f"c{i}" for i in range(E_CTG)]
+    ctg_len = np.full(E_CTG, E_CTG_LEN, np.uint32)
+    sequences = _sequences({name: E_CTG_LEN for name in ctg_names})
+    pairs = {(_node_name(key >> 32), _node_name(key & 0xFFFFFFFF)): None for key in keys}  # pair i is keys[i]
+    assert len(pairs) == len(keys)
+    # the host's table is the simulation's, slot for slot
+    table = capi.pair_table(keys, n_slots=E_SLOTS, lib_path=dev.lib_path)
+    sk, sv = probe_table(keys, E_SLOTS)
+    assert table[0].tolist() == sk and table[1].tolist() == sv
+    with pytest.raises(ValueError):  # 33 keys in 64 slots
+        capi.pair_table(keys + [unused], n_slots=E_SLOTS, lib_path=dev.lib_path)
+    # the restatement alone: what the comparison below relies on
+    want, ids = gapfill.restated_candidates(pairs, vp, sequences, K)
+    assert len(ids) == len(kinds)
+    per_read = np.bincount(want["read"], minlength=len(kinds)).tolist()
+    with open(vp) as fh:
+        n_maps = [len(entries) for _rid, entries in formats.parse_verbose(fh)]
+    tried = sum(n * (n - 1) // 2 for n in n_maps)
+    assert 0 < len(want) < tried and n_maps[-1] == 5 and kinds[-1] == "five" and tried == len(kinds) - 1 + 10
+    for r, kind in enumerate(kinds):
+        mine = want[want["read"] == r]
+        via = (mine["flags"] & capi.NTL_GAPSEL_VIA_REVCOMP) != 0
+        if kind == "present":
+            assert per_read[r] == 1 and mine["pair"][0] == r and not via[0]
+        elif kind == "revcomp":
+            assert per_read[r] == 1 and via[0] and gsel_slot(keys[int(mine["pair"][0])], E_SLOTS) in (62, 30, 3, 40, 41, 45, 50)
+        elif kind == "absent":
+            assert per_read[r] == 0
+        else:
+            assert 2 <= per_read[r] <= 6 and {gsel_slot(keys[int(p)], E_SLOTS) for p in mine["pair"]} >= {62, 30}
+    assert sum(1 for kind in kinds if kind == "revcomp") == 11 and sum(1 for kind in kinds if kind == "absent") == 15
+    # the device, the file whole and in blocks of a few reads
+    for max_bytes in (0, SMALL_BLOCK):
+        got, first = [], 0
+        for block in formats.read_verbose(vp, ctg_names, max_bytes=max_bytes, lib_path=dev.lib_path):
+            cands = dev.gap_select(block, ctg_len, K, table)
+            cands["read"] += first
+            first += len(block.names)
+            got.append(cands)
+        assert first == len(kinds) and (len(got) == 1 if not max_bytes else len(got) > 5)
+        got = np.concatenate(got)
+        assert len(got) == len(want), f"max_bytes {max_bytes}: {len(got)} candidates, the restated reference gives {len(want)}"
+        for i in np.flatnonzero(got != want)[:5]:
+            raise AssertionError(f"max_bytes {max_bytes}, record {i} (read {kinds[int(want[i]['read'])]}): {got[i]}, the restated reference gives {want[i]}")
+    # one key more, put into the empty slot behind the cluster: more than half full, refused as in d.
+    full = (table[0].copy(), table[1].copy())
+    full[0][19], full[1][19] = unused, len(keys)
+    (block,) = formats.read_verbose(vp, ctg_names, lib_path=dev.lib_path)
+    with pytest.raises(capi.NtlError) as e:
+        dev.gap_select(block, ctg_len, K, full)
+    assert e.value.code == capi.NTL_EINVAL
+    dev.sync()
+
+
 # ---------------------------------------------------------------- under the SIMT mock
 
 @pytest.fixture(scope="module")
@@ -358,6 +544,10 @@ def test_sim_reader_refusals(sim_dev, tmp_path):
 
 def test_sim_refusals(sim_dev, tmp_path):
     check_refusals(sim_dev, tmp_path)
+
+
+def test_sim_pair_clusters(sim_dev, tmp_path):
+    check_pair_clusters(sim_dev, tmp_path)
 
 
 # ---------------------------------------------------------------- on the GPU
@@ -393,3 +583,8 @@ def test_gpu_reader_refusals(gpu_dev, tmp_path):
 @pytest.mark.gpu
 def test_gpu_refusals(gpu_dev, tmp_path):
     check_refusals(gpu_dev, tmp_path)
+
+
+@pytest.mark.gpu
+def test_gpu_pair_clusters(gpu_dev, tmp_path):
+    check_pair_clusters(gpu_dev, tmp_path)
