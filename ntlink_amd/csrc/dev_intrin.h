@@ -1,5 +1,10 @@
 /* gfx950 instruction wrappers used by the kernels (the SIMT mock under tests/sim supplies its
- * own file of the same name with portable bodies). */
+ * own file of the same name with portable bodies).
+ *
+ * The comment above a wrapper is its definition and its contract: the operand range, and which lanes have to be active.  A wrapper
+ * that works lane by lane says nothing about lanes: any active set.  The cross-lane ones say "all 64 lanes active": with fewer the
+ * result is unspecified here (DPP and v_readlane read inactive lanes' registers) and the mock's shuffle waits for lanes that never
+ * arrive.  tests/test_intrinsics.py runs every wrapper of both files over the same operands against the definition. */
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -10,10 +15,11 @@ __device__ __forceinline__ uint32_t ntl_alignbit(uint32_t hi, uint32_t lo, uint3
     return __builtin_amdgcn_alignbit(hi, lo, sh);
 }
 
-/* (x >> off) & ((1 << width) - 1) : v_bfe_u32 */
+/* (x >> off) & ((1 << width) - 1), off and width in 0..31 each (the instruction takes five bits of both: width 32 is NOT the whole
+   word; the call sites pass width 8 and off 0, 8, 16, 24) : v_bfe_u32 */
 __device__ __forceinline__ uint32_t ntl_bfe(uint32_t x, uint32_t off, uint32_t width) { return __builtin_amdgcn_ubfe(x, off, width); }
 
-/* (a & mask) | (b & ~mask) : v_bfi_b32 (written as asm: the compiler re-associates the C form into more instructions) */
+/* (a & MASK) | (b & ~MASK), MASK an inline constant (0..64, -16..-1 as u32) : v_bfi_b32 (written as asm: the compiler re-associates the C form into more instructions) */
 template <uint32_t MASK>
 __device__ __forceinline__ uint32_t ntl_bfi(uint32_t a, uint32_t b)
 {
@@ -22,7 +28,7 @@ __device__ __forceinline__ uint32_t ntl_bfi(uint32_t a, uint32_t b)
     return r;
 }
 
-/* (acc << 1) | (a != b): v_cmp_ne_u32 + v_addc_co_u32 (acc + acc + carry) */
+/* (acc << 1) | (a != b), bit 31 of acc is dropped, as in the three below: v_cmp_ne_u32 + v_addc_co_u32 (acc + acc + carry) */
 __device__ __forceinline__ uint32_t ntl_shl1_or_ne(uint32_t acc, uint32_t a, uint32_t b)
 {
     uint32_t r;
@@ -47,7 +53,8 @@ __device__ __forceinline__ uint32_t ntl_shl1_or_lt_diff(uint32_t acc, uint32_t a
     return r;
 }
 
-/* minimum over the 16 lanes of a row (lanes 16i..16i+15), result in every lane: four v_min_u32 with DPP row rotations */
+/* minimum over the 16 lanes of a row (lanes 16i..16i+15), result in every lane: four v_min_u32 with DPP row rotations.
+   All 64 lanes active. */
 __device__ __forceinline__ uint32_t ntl_row_min16(uint32_t v)
 {
     uint32_t t;
@@ -66,7 +73,8 @@ __device__ __forceinline__ uint32_t ntl_shl1_or_eq(uint32_t acc, uint32_t a, uin
     return r;
 }
 
-/* minimum / sum over the 4 lanes of a quad, result in every lane: DPP quad_perm [1,0,3,2] then [2,3,0,1] */
+/* minimum / sum (mod 2^32) over the 4 lanes of a quad, result in every lane: DPP quad_perm [1,0,3,2] then [2,3,0,1].
+   All 64 lanes active. */
 __device__ __forceinline__ uint32_t ntl_quad_min(uint32_t v)
 {
     uint32_t t;
@@ -81,7 +89,8 @@ __device__ __forceinline__ uint32_t ntl_quad_sum(uint32_t v)
     return v;
 }
 
-/* minimum over the 64 lanes of a wavefront, in every lane (uniform): the rows' minima, then four v_readlane and three s_min */
+/* minimum over the 64 lanes of a wavefront, in every lane (uniform): the rows' minima, then four v_readlane and three s_min.
+   All 64 lanes active (lanes 0, 16, 32 and 48 are read whether they are or not). */
 __device__ __forceinline__ uint32_t ntl_wave_min(uint32_t v)
 {
     v = ntl_row_min16(v);
@@ -91,6 +100,7 @@ __device__ __forceinline__ uint32_t ntl_wave_min(uint32_t v)
     return ab < cd ? ab : cd;
 }
 
+/* maximum over the 16 lanes of a row, as ntl_row_min16.  All 64 lanes active. */
 __device__ __forceinline__ uint32_t ntl_row_max16(uint32_t v)
 {
     uint32_t t;
@@ -101,7 +111,7 @@ __device__ __forceinline__ uint32_t ntl_row_max16(uint32_t v)
     return v;
 }
 
-/* x + x, kept an addition (the compiler turns it into the slower v_lshlrev_b32 x, 1) */
+/* x + x (mod 2^32), kept an addition (the compiler turns it into the slower v_lshlrev_b32 x, 1) */
 __device__ __forceinline__ uint32_t ntl_double(uint32_t x)
 {
     uint32_t r;
@@ -112,25 +122,30 @@ __device__ __forceinline__ uint32_t ntl_double(uint32_t x)
 /* bit reversal of a 32-bit word: v_bfrev_b32 */
 __device__ __forceinline__ uint32_t ntl_brev(uint32_t x) { return __builtin_bitreverse32(x); }
 
-/* number of set bits of `mask` below this lane: v_mbcnt_lo/hi */
+/* number of set bits of `mask` below this lane, any mask: v_mbcnt_lo/hi.  Any active set (the call sites sit behind a lane's own
+   condition, with a ballot taken in front of it). */
 __device__ __forceinline__ uint32_t ntl_mbcnt(unsigned long long mask)
 {
     return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
 }
 
 /* x*d + k in IEEE double with two roundings (no FMA contraction): the reference computes
- * `args.x * abs(...) + args.k` in Python floats (bin/ntlink_utils.py:230-231). */
+ * `args.x * abs(...) + args.k` in Python floats (bin/ntlink_utils.py:230-231).  The pragma is what keeps the two apart:
+ * __dadd_rn(__dmul_rn(x, d), k) is a plain x * d + k to the compiler, which its default contraction made ONE v_fma_f64. */
 __device__ __forceinline__ double ntl_mul_add_rn(double x, double d, double k)
 {
-    return __dadd_rn(__dmul_rn(x, d), k);
+#pragma clang fp contract(off)
+    const double m = x * d;
+    return m + k;
 }
 
 /* streaming (non-temporal) 64-bit global accesses: data touched once should not evict reused lines from L2 */
 __device__ __forceinline__ uint64_t ntl_stream_load(const uint64_t *p) { return __builtin_nontemporal_load(p); }
 __device__ __forceinline__ void ntl_stream_store(uint64_t *p, uint64_t v) { __builtin_nontemporal_store(v, p); }
 
-/* inclusive prefix sum over the 64 lanes of a wavefront: four DPP row shifts inside the rows of 16, then the row totals
-   broadcast forward (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) -- six v_add_u32 with DPP operands */
+/* inclusive prefix sum (mod 2^32) over the 64 lanes of a wavefront: four DPP row shifts inside the rows of 16, then the row totals
+   broadcast forward (row_bcast:15 into rows 1 and 3, row_bcast:31 into rows 2 and 3) -- six v_add_u32 with DPP operands.
+   All 64 lanes active. */
 __device__ __forceinline__ uint32_t ntl_wave_incl_scan(uint32_t v)
 {
     v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x111, 0xF, 0xF, false); /* row_shr:1 */
@@ -143,7 +158,8 @@ __device__ __forceinline__ uint32_t ntl_wave_incl_scan(uint32_t v)
 }
 
 /* Wave-synchronous hand-off through LDS: LDS operations of one wavefront execute in program order, so lanes of a wavefront may
-   exchange data through LDS without a workgroup barrier -- the compiler only has to keep the accesses in order (no instruction). */
+   exchange data through LDS without a workgroup barrier -- the compiler only has to keep the accesses in order (no instruction).
+   All 64 lanes active (wave-uniform flow: the mock's form is a barrier over the wavefront). */
 __device__ __forceinline__ void ntl_wave_sync()
 {
     __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -151,10 +167,11 @@ __device__ __forceinline__ void ntl_wave_sync()
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
-/* the value of the first active lane in every lane (an SGPR): v_readfirstlane_b32 */
+/* the value of the first active lane in every lane (an SGPR): v_readfirstlane_b32.  All 64 lanes active: every call site is in
+   wave-uniform flow, where the first active lane is lane 0 (which is what the mock reads). */
 __device__ __forceinline__ uint32_t ntl_readfirstlane(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
 
-/* four consecutive words from a pointer that is only 4-byte aligned: one global_load_dwordx4 */
+/* four consecutive words from a pointer into global memory that is only 4-byte aligned: one global_load_dwordx4 */
 struct __attribute__((packed, aligned(4))) ntl_u32x4_a4 { uint32_t x, y, z, w; };
 __device__ __forceinline__ uint4 ntl_load4_a4(const uint32_t *p)
 {
@@ -179,7 +196,8 @@ typedef __attribute__((address_space(3))) const uint64_t ntl_lds_cu64;
 /* hides a value's origin from the optimiser (no instruction) */
 #define NTL_OPAQUE(v) asm volatile("" : "+v"(v))
 
-/* *p++ = (v & ~mask) | T for a pointer into LDS and a constant T, as the three vector instructions it is: v_bfi_b32 with T as an
+/* *p++ = (v & ~mask) | (T & mask) for a pointer into LDS and a constant T >= 0 -- (v & ~mask) | T at the call sites, whose mask
+   covers every bit of their T -- as the three vector instructions it is: v_bfi_b32 with T as an
    inline constant, ds_write_b32, v_add_u32 (the compiler makes a v_mov of the constant, a temporary of the incremented pointer
    and a v_mov of that).  T > 64 is no inline constant, and a VOP3 instruction takes no literal on this architecture: such a T comes
    from a scalar register loaded right there (s_mov_b32: the scalar unit's issue slot, not the vector ALU's, and nothing for the
@@ -202,7 +220,7 @@ __device__ __forceinline__ void ntl_lds_push_tagged(uint32_t *&p, uint32_t mask,
     p = (uint32_t *)q;
 }
 
-/* a - b, 0 where it would wrap: v_sub_u32 with the clamp bit */
+/* a - b, 0 where it would wrap (a < b): v_sub_u32 with the clamp bit */
 __device__ __forceinline__ uint32_t ntl_sub_sat(uint32_t a, uint32_t b) { return __builtin_elementwise_sub_sat(a, b); }
 
 /* minimum of three: v_min3_u32 */
@@ -212,7 +230,7 @@ __device__ __forceinline__ uint32_t ntl_min3(uint32_t a, uint32_t b, uint32_t c)
     return m < c ? m : c;
 }
 
-/* bit i: k_i <= lim, bit 4 set: four compare + add-with-carry pairs as ONE asm statement (between separate statements the compiler
+/* bit i (i = 0..3): k_i <= lim; bit 4 set; the rest 0: four compare + add-with-carry pairs as ONE asm statement (between separate statements the compiler
    pads with s_nop) */
 __device__ __forceinline__ uint32_t ntl_le4_mask(uint32_t k0, uint32_t k1, uint32_t k2, uint32_t k3, uint32_t lim)
 {

@@ -466,21 +466,12 @@ extern "C" int ntl_prof_get(ntl_ctx *c, const char *name, double *total_ms, uint
 static int device_scan(ntl_ctx *c, const uint32_t *in, uint32_t *out, uint64_t n, uint32_t *total_host, unsigned batch = 1,
                        uint32_t *sums_dev = nullptr, int sid = SID_MAIN)
 {
-    uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
-    if (tiles == 0) tiles = 1;
+    const uint64_t tiles = scan_tile_count(n);
     DevBuf tile;
     int rc;
     hipStream_t st = c->s(sid);
     if ((rc = tile.alloc(c, tiles * 4 * batch, sid))) return rc;
-    hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)tiles, batch), dim3(SCAN_NT), 0, st, in, n, tile.as<uint32_t>(), n + 1, tiles);
-    if (tiles <= 4096) { /* two launches: every workgroup of the second sums the tiles in front of its own */
-        hipLaunchKernelGGL(scan_down_self_kernel, dim3((unsigned)tiles, batch), dim3(SCAN_NT), 0, st, in, out, n,
-                           (const uint32_t *)tile.as<uint32_t>(), n + 1, tiles, sums_dev);
-    } else {
-        hipLaunchKernelGGL(scan_tiles_kernel, dim3(1, batch), dim3(SCAN_NT), 0, st, tile.as<uint32_t>(), tiles, out + n, n + 1, sums_dev);
-        hipLaunchKernelGGL(scan_down_kernel, dim3((unsigned)tiles, batch), dim3(SCAN_NT), 0, st, in, out, n,
-                           (const uint32_t *)tile.as<uint32_t>(), n + 1, tiles);
-    }
+    scan_launch(st, in, out, n, batch, tile.as<uint32_t>(), sums_dev);
     HIPCHK(c, hipGetLastError());
     if (total_host) {
         for (unsigned y = 0; y < batch; y++)

@@ -122,3 +122,33 @@ __global__ __launch_bounds__(SCAN_NT) void scan_down_self_kernel(const uint32_t 
         if (extra) extra[blockIdx.y] = before + total;
     }
 }
+
+/* Up to this many tiles the scan takes two launches (scan_reduce_kernel + scan_down_self_kernel: tiles^2 / 2 words read), above it
+ * three (scan_reduce_kernel + scan_tiles_kernel + scan_down_kernel). */
+#define SCAN_SELF_MAX_TILES 4096
+
+/* tiles of one array of n items (one for n = 0: out[0] = 0 is still to be written); the tile buffer holds this many words per array */
+static inline uint64_t scan_tile_count(uint64_t n)
+{
+    const uint64_t tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
+    return tiles ? tiles : 1;
+}
+
+/* The launches of `batch` independent exclusive scans of equal length on stream st: array y is in + y*(n+1) -> out + y*(n+1),
+ * out[n] of each = its sum (arrays hold n+1 entries; in may equal out); `tile` holds scan_tile_count(n) * batch words; with sums_dev
+ * the sums also go to sums_dev[y].  self_max_tiles is SCAN_SELF_MAX_TILES everywhere in the product (a test passes 0 to take the
+ * three-launch path at a small n). */
+static inline void scan_launch(hipStream_t st, const uint32_t *in, uint32_t *out, uint64_t n, unsigned batch, uint32_t *tile,
+                               uint32_t *sums_dev, uint64_t self_max_tiles = SCAN_SELF_MAX_TILES)
+{
+    const uint64_t tiles = scan_tile_count(n);
+    hipLaunchKernelGGL(scan_reduce_kernel, dim3((unsigned)tiles, batch), dim3(SCAN_NT), 0, st, in, n, tile, n + 1, tiles);
+    if (tiles <= self_max_tiles) { /* two launches: every workgroup of the second sums the tiles in front of its own */
+        hipLaunchKernelGGL(scan_down_self_kernel, dim3((unsigned)tiles, batch), dim3(SCAN_NT), 0, st, in, out, n,
+                           (const uint32_t *)tile, n + 1, tiles, sums_dev);
+    } else {
+        hipLaunchKernelGGL(scan_tiles_kernel, dim3(1, batch), dim3(SCAN_NT), 0, st, tile, tiles, out + n, n + 1, sums_dev);
+        hipLaunchKernelGGL(scan_down_kernel, dim3((unsigned)tiles, batch), dim3(SCAN_NT), 0, st, in, out, n,
+                           (const uint32_t *)tile, n + 1, tiles);
+    }
+}
