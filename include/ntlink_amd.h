@@ -187,6 +187,45 @@ int ntl_batch_mask(ntl_ctx *ctx, const ntl_batch *src, uint64_t n, const uint32_
                    const uint32_t *keep_hi, ntl_batch **out);
 int ntl_batch_download_n(const ntl_batch *b, char *seqs, uint64_t *offsets);
 
+/* ---- resident bytes and the stitch (the gap filler's output sequences) ---------------------- */
+
+/* The reference's gap filler ends by concatenating, per path line, slices of scaffolds, slices of the chosen reads and runs of N
+ * into the output FASTA (print_gap_filled_sequences, bin/ntlink_patch_gaps.py:533-598): a `-` node and a read that lies the other way
+ * round are reverse-complemented, the base behind an overlap join and (--soft_mask) the read piece are lower-cased.  The output
+ * carries the input's bytes -- lower case, N, IUPAC codes -- which a batch does not keep, so the records are resident a second time,
+ * as they were read:
+ *   ntl_ascii_create: record i = bytes[offsets[i] .. offsets[i+1]), shorter than 2^32 bytes, uploaded as it is.  The caller's
+ *       arrays are free when the call returns; page-locked memory (ntl_host_alloc) makes the upload one DMA.
+ * ntl_stitch writes the concatenation of n_segs segments, in order (csrc/stitch_kernels.h; the work is divided by output bytes):
+ *   - a copy segment {store, rec, lo, hi, flags}: bytes [lo, hi) of record rec of stores[store].  NTL_STITCH_REVCOMP: the piece
+ *     reversed, every byte through the reference's table (:50-53: ACGTUNMRWSYKVHDB and their lower case; every other byte as it is).
+ *     NTL_STITCH_LOWER: then A-Z -> a-z (Python's .lower() on ASCII).  NTL_STITCH_LOWER_FIRST: the piece's first OUTPUT byte alone; an
+ *     empty piece lowers nothing, neither its own nor the next piece's.
+ *   - a fill segment {NTL_STITCH_FILL, byte, lo, hi, 0}: hi - lo copies of the byte (runs of N, the newline; header lines come
+ *     from a small store of `>id\n` records)
+ *   - NTL_EINVAL with a message ("segment i: ..."): a store or a record out of range, lo above hi, hi beyond the record, unknown
+ *     flag bits, flags on a fill
+ *   - n_segs == 0, or nothing but empty segments, gives an empty result; output offsets are 64-bit
+ * ntl_stitch only QUEUES (the segments are copied): stores and arrays may go as soon as it returns.  ntl_stitched_copy waits and
+ * copies bytes [lo, hi) of the result, so that a writer can take it in pieces into page-locked memory.  Event name for
+ * ntl_prof_get: "stitch" (the kernel), "ascii_upload". */
+typedef struct ntl_ascii ntl_ascii;
+typedef struct ntl_stitched ntl_stitched;
+typedef struct { uint32_t store, rec, lo, hi, flags; } ntl_stitch_seg;
+#define NTL_STITCH_FILL 0xFFFFFFFFu
+#define NTL_STITCH_REVCOMP 1u
+#define NTL_STITCH_LOWER 2u
+#define NTL_STITCH_LOWER_FIRST 4u
+int ntl_ascii_create(ntl_ctx *ctx, const char *bytes, const uint64_t *offsets, uint64_t nrec, ntl_ascii **out);
+void ntl_ascii_destroy(ntl_ascii *a);
+uint64_t ntl_ascii_nrec(const ntl_ascii *a);
+uint64_t ntl_ascii_bytes(const ntl_ascii *a);
+int ntl_stitch(ntl_ctx *ctx, const ntl_ascii *const *stores, uint32_t n_stores, const ntl_stitch_seg *segs, uint64_t n_segs,
+               ntl_stitched **out);
+uint64_t ntl_stitched_bytes(const ntl_stitched *s);
+int ntl_stitched_copy(const ntl_stitched *s, uint64_t lo, uint64_t hi, char *out);
+void ntl_stitched_destroy(ntl_stitched *s);
+
 /* ---- sketch ---------------------------------------------------------------------------- */
 
 /* Asynchrony.  ntl_sketch_run[_indexed] and ntl_map_run only QUEUE device work and return; no size comes back to the host

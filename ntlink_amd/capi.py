@@ -21,6 +21,7 @@ SYMBOLS = [
     "ntl_prof_enable", "ntl_prof_reset", "ntl_prof_get",
     "ntl_batch_create", "ntl_batch_create_packed", "ntl_batch_create_packed_at", "ntl_packed_words", "ntl_batch_destroy", "ntl_batch_nseq", "ntl_batch_bases", "ntl_host_alloc", "ntl_host_free",
     "ntl_synth_genome", "ntl_synth_slices", "ntl_batch_download", "ntl_batch_mask", "ntl_batch_download_n",
+    "ntl_ascii_create", "ntl_ascii_destroy", "ntl_ascii_nrec", "ntl_ascii_bytes", "ntl_stitch", "ntl_stitched_bytes", "ntl_stitched_copy", "ntl_stitched_destroy",
     "ntl_sketch_run", "ntl_sketch_run_indexed", "ntl_sketch_run_for_map", "ntl_sketch_has_records", "ntl_sketch_destroy", "ntl_sketch_nseq", "ntl_sketch_count", "ntl_sketch_download",
     "ntl_sketch_strips", "ntl_sketch_redo_strips", "ntl_sketch_fallback_strips", "ntl_sketch_from_lists", "ntl_sketch_plan", "ntl_sketch_wait", "ntl_mapres_wait",
     "ntl_sketch_from_host", "ntl_overlap_filter",
@@ -49,6 +50,8 @@ NTL_GAP_NOT_TWO, NTL_GAP_SRC_MIXED_STRANDS, NTL_GAP_TGT_MIXED_STRANDS, NTL_GAP_S
 GAP_CAND_DT = np.dtype([(nm, "<u4") for nm in ("pair", "read", "anchors", "flags", "source_ctg_cut", "source_read_cut", "target_ctg_cut",
                                                 "target_read_cut")])  # ntl_gap_cand
 NTL_GAPSEL_VALID, NTL_GAPSEL_NEGATIVE, NTL_GAPSEL_VIA_REVCOMP = 1, 2, 4
+STITCH_SEG_DT = np.dtype([(nm, "<u4") for nm in ("store", "rec", "lo", "hi", "flags")])  # ntl_stitch_seg
+NTL_STITCH_FILL, NTL_STITCH_REVCOMP, NTL_STITCH_LOWER, NTL_STITCH_LOWER_FIRST = 0xFFFFFFFF, 1, 2, 4
 NO_CTG = 0xFFFFFFFF  # ntl_mapping.ctg of a name that is not in the reader's table
 
 
@@ -130,6 +133,16 @@ def load(path=None):
     L.ntl_batch_download.argtypes = [vp, vp, u64p]
     L.ntl_batch_mask.argtypes = [vp, vp, C.c_uint64, u32p, u32p, u32p, C.POINTER(vp)]
     L.ntl_batch_download_n.argtypes = [vp, vp, u64p]
+    L.ntl_ascii_create.argtypes = [vp, vp, u64p, C.c_uint64, C.POINTER(vp)]
+    L.ntl_ascii_destroy.argtypes = [vp]
+    L.ntl_ascii_destroy.restype = None
+    for nm in ("ntl_ascii_nrec", "ntl_ascii_bytes", "ntl_stitched_bytes"):
+        getattr(L, nm).argtypes = [vp]
+        getattr(L, nm).restype = C.c_uint64
+    L.ntl_stitch.argtypes = [vp, C.POINTER(vp), C.c_uint32, vp, C.c_uint64, C.POINTER(vp)]
+    L.ntl_stitched_copy.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
+    L.ntl_stitched_destroy.argtypes = [vp]
+    L.ntl_stitched_destroy.restype = None
     L.ntl_sketch_run.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.ntl_sketch_run_indexed.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
     L.ntl_sketch_run_for_map.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
@@ -297,6 +310,40 @@ class Batch(_Handle):
         buf = np.empty(max(self.bases, 1), np.uint8)
         self.dev._chk(self.dev.L.ntl_batch_download_n(self.ptr, buf.ctypes.data, _ptr(off, C.c_uint64)))
         return buf[:int(off[-1])], off
+
+
+class Ascii(_Handle):
+    """Records resident on the device as the bytes they were read as (ntl_ascii): the sources of Device.stitch."""
+    _destroy = "ntl_ascii_destroy"
+
+    @property
+    def nrec(self):
+        return int(self.dev.L.ntl_ascii_nrec(self.ptr))
+
+    @property
+    def nbytes(self):
+        return int(self.dev.L.ntl_ascii_bytes(self.ptr))
+
+
+class Stitched(_Handle):
+    """The text Device.stitch assembled, on the device until it is copied."""
+    _destroy = "ntl_stitched_destroy"
+
+    @property
+    def nbytes(self):
+        return int(self.dev.L.ntl_stitched_bytes(self.ptr))
+
+    def copy(self, lo, hi, out):
+        """bytes [lo, hi) into the uint8 array `out` (Device.pinned_empty: one DMA); waits for the device"""
+        if len(out) < hi - lo:
+            raise ValueError("the destination is smaller than the range")
+        self.dev._chk(self.dev.L.ntl_stitched_copy(self.ptr, int(lo), int(hi), out.ctypes.data))
+        return out[:hi - lo]
+
+    def download(self):
+        """the whole text as a uint8 array"""
+        n = self.nbytes
+        return self.copy(0, n, np.empty(max(n, 1), np.uint8))[:n]
 
 
 class Sketch(_Handle):
@@ -652,6 +699,36 @@ class Device:
         self._chk(self.L.ntl_batch_mask(self.ptr, src.ptr, len(sq), _ptr(sq, C.c_uint32), _ptr(lo, C.c_uint32), _ptr(hi, C.c_uint32),
                                         C.byref(p)))
         return Batch(self, p)
+
+    def ascii(self, seqs, offsets=None):
+        """Records resident as they are (ntl_ascii_create): seqs as Device.batch takes them -- a list of bytes, or one contiguous
+        bytes / uint8 buffer with offsets[n+1]."""
+        if offsets is None:
+            lens = np.fromiter((len(s) for s in seqs), np.uint64, len(seqs))
+            offsets = np.zeros(len(seqs) + 1, np.uint64)
+            np.cumsum(lens, out=offsets[1:])
+            buf = np.frombuffer(b"".join(seqs), np.uint8)
+        else:
+            buf = seqs if isinstance(seqs, np.ndarray) else np.frombuffer(seqs, np.uint8)
+            offsets = np.ascontiguousarray(offsets, np.uint64)
+        if len(buf) == 0:
+            buf = np.zeros(1, np.uint8)
+        p = C.c_void_p()
+        self._chk(self.L.ntl_ascii_create(self.ptr, buf.ctypes.data, _ptr(offsets, C.c_uint64), len(offsets) - 1, C.byref(p)))
+        return Ascii(self, p)
+
+    def stitch(self, stores, segs):
+        """The concatenation of the segments (ntl_stitch, csrc/stitch_kernels.h): stores = a list of Ascii, segs = STITCH_SEG_DT
+        records (or tuples) {store, rec, lo, hi, flags} -- bytes [lo, hi) of record rec of stores[store], reverse-complemented
+        (NTL_STITCH_REVCOMP), lower-cased (NTL_STITCH_LOWER) or with the first output byte lower-cased (NTL_STITCH_LOWER_FIRST);
+        store NTL_STITCH_FILL: hi - lo copies of the byte `rec`.  Only queues; -> Stitched."""
+        sg = np.ascontiguousarray(segs if isinstance(segs, np.ndarray) else np.array(list(segs), STITCH_SEG_DT), STITCH_SEG_DT)
+        if sg.ndim != 1:
+            raise ValueError("segs must be one-dimensional")
+        ptrs = (C.c_void_p * max(len(stores), 1))(*[st.ptr for st in stores])
+        p = C.c_void_p()
+        self._chk(self.L.ntl_stitch(self.ptr, ptrs, len(stores), sg.ctypes.data if len(sg) else None, len(sg), C.byref(p)))
+        return Stitched(self, p)
 
     def sketch(self, batch, k, w, index=None, records=True):
         """index: the contig Index the sketch will be mapped against -- its minimizers are then looked up while they are emitted

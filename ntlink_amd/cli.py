@@ -3,6 +3,7 @@
   indexlr_main      `indexlr --long --pos --strand [--len] -k K -w W [-t T] FILE|-`   (ntLink:199,223)
   ntlink_pair_main  `ntlink_pair.py ...` with the reference's argparse               (bin/ntlink_pair.py:509-536)
   ntlink_main       `ntLink pair target= reads= [k= w= ...]` make-style key=value    (ntLink:8-89,165)
+  patch_gaps_main   `ntlink_patch_gaps.py ...` with the reference's argparse         (bin/ntlink_patch_gaps.py:760-784)
 """
 import argparse
 import os
@@ -80,6 +81,46 @@ def ntlink_pair_main(argv=None):
             dev.close()
     except Exception as exc:
         raise NtlinkPairError("ntLink pairing stage encountered an error..") from exc
+    return 0
+
+
+def patch_gaps_parser():
+    p = argparse.ArgumentParser(description="Use minimizer mappings to fill gaps")
+    p.add_argument("--path", help="Input path file for gap patching", required=True, type=str)
+    p.add_argument("--mappings", help="ntLink verbose mapping TSV", required=True, type=str)
+    p.add_argument("--trims", help="ntLink file listing trims made", required=True, type=str)
+    p.add_argument("-s", help="Input scaffolds", required=True, type=str)
+    p.add_argument("--reads", help="Input reads", required=True, type=str, nargs="+")
+    p.add_argument("-z", help="Minimum contig size (bp) [1000]", type=int, required=False, default=1000)
+    p.add_argument("-k", help="Kmer size used in minimizer step [20]", type=int, required=False, default=20)
+    p.add_argument("-w", help="Window size used in minimizer step [10]", type=int, required=False, default=10)
+    p.add_argument("-t", help="Number of threads [4]", type=int, required=False, default=4)
+    p.add_argument("--large_k", help="K-mer size used in generating verbose mapping TSV", required=True, type=int)
+    p.add_argument("-x", help="Fudge factor allowed between mapping block lengths on read and assembly "
+                              "for re-mapping reads", type=float, required=False, default=0)
+    p.add_argument("--min_gap", help="Minimum gap size [20]", type=int, default=20)
+    p.add_argument("-o", help="Output file name", required=False, default="ntLink_patch_gaps_out.fa", type=str)
+    p.add_argument("--stringent", help="If specified, will only use lower k/w re-mapping for filling gaps,"
+                                       " will not fall back on original anchors", action="store_true")
+    p.add_argument("--soft_mask", help="If specified, will soft mask the filled gap", action="store_true")
+    p.add_argument("--sensitive", help="Run more sensitive read mapping", action="store_true")
+    p.add_argument("--verbose", help="Verbose logging - print out trimmed scaffolds without gaps", action="store_true")
+    p.add_argument("-v", "--version", action="version", version="ntLink v1.3.11")
+    p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    return p
+
+
+def patch_gaps_main(argv=None):
+    """The gap-filling stage (gapfill.patch_gaps): the reference's arguments, parameter block and log lines; `-t` is accepted (the
+    native readers have their own thread count)."""
+    a = patch_gaps_parser().parse_args(argv)
+    from . import gapfill
+    gapfill.print_parameters(a)
+    dev = _device(a.device)
+    try:
+        gapfill.patch_gaps(a, dev)
+    finally:
+        dev.close()
     return 0
 
 

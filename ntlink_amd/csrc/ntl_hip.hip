@@ -37,6 +37,7 @@
 #include "pack_kernels.h"
 #include "synth_kernels.h"
 #include "mask_kernels.h"
+#include "stitch_kernels.h"
 #include "overlap_kernels.h"
 #include "format_kernels.h"
 
@@ -953,6 +954,157 @@ extern "C" int ntl_batch_download_n(const ntl_batch *b, char *seqs, uint64_t *of
     HIPCHK(c, hipMemcpyAsync(seqs, tmp.p, t, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return NTL_OK;
+}
+
+/* ------------------------------------------------------------------ resident bytes, the stitch ---------- */
+
+/* Records resident as the bytes they were read as (a batch keeps neither lower case nor IUPAC codes): the sources of ntl_stitch. */
+struct ntl_ascii {
+    ntl_ctx *c;
+    std::vector<uint64_t> off; /* [nrec + 1], from 0 */
+    DevBuf bytes;
+};
+
+extern "C" int ntl_ascii_create(ntl_ctx *c, const char *bytes, const uint64_t *off, uint64_t nrec, ntl_ascii **out)
+{
+    if (!c || !out || !off || (!bytes && nrec)) return NTL_EINVAL;
+    *out = nullptr;
+    for (uint64_t i = 0; i < nrec; i++) {
+        if (off[i + 1] < off[i]) return fail(c, NTL_EINVAL, "offsets must be non-decreasing");
+        if (off[i + 1] - off[i] >= 0xFFFFFFFFull) return fail(c, NTL_EINVAL, "record " + std::to_string(i) + " is longer than 2^32 bytes");
+    }
+    std::unique_ptr<ntl_ascii> a(new ntl_ascii());
+    a->c = c;
+    a->off.resize(nrec + 1);
+    for (uint64_t i = 0; i <= nrec; i++) a->off[i] = off[i] - off[0];
+    const uint64_t total = a->off[nrec];
+    (void)hipSetDevice(c->device);
+    if (int rc = a->bytes.alloc(c, total + 16)) return rc;
+    if (total) {
+        ProfSpan span(c, "ascii_upload");
+        HIPCHK(c, hipMemcpyAsync(a->bytes.p, bytes + off[0], total, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, main_wait(c)); /* the caller's arrays are free again */
+    *out = a.release();
+    return NTL_OK;
+}
+
+extern "C" void ntl_ascii_destroy(ntl_ascii *a)
+{
+    if (!a) return;
+    (void)hipSetDevice(a->c->device);
+    delete a; /* the block returns to MAIN's cache: whatever is queued there and reads it runs first */
+}
+extern "C" uint64_t ntl_ascii_nrec(const ntl_ascii *a) { return a ? a->off.size() - 1 : 0; }
+extern "C" uint64_t ntl_ascii_bytes(const ntl_ascii *a) { return a ? a->off.back() : 0; }
+
+struct ntl_stitched {
+    ntl_ctx *c;
+    uint64_t total = 0;
+    DevBuf out, aux;
+    std::vector<uint64_t> host_aux; /* source of the asynchronous upload: outlives it (`queued`) */
+    hipEvent_t queued = nullptr;    /* on MAIN behind the kernel */
+};
+
+/* The output text of the segments, in order (stitch_kernels.h).  Only queues: the stores may be destroyed at once, the result is
+ * waited for by ntl_stitched_copy. */
+extern "C" int ntl_stitch(ntl_ctx *c, const ntl_ascii *const *stores, uint32_t n_stores, const ntl_stitch_seg *segs, uint64_t n_segs,
+                          ntl_stitched **out)
+{
+    if (!c || !out || (n_stores && !stores) || (n_segs && !segs)) return NTL_EINVAL;
+    *out = nullptr;
+    for (uint32_t i = 0; i < n_stores; i++)
+        if (!stores[i] || stores[i]->c != c) return fail(c, NTL_EINVAL, "store " + std::to_string(i) + " is not a store of this context");
+    std::unique_ptr<ntl_stitched> r(new ntl_stitched());
+    r->c = c;
+    /* the device's tables in one block: the complement table (256 bytes), off[n + 1], seg[n] -- n counts the non-empty segments */
+    std::vector<uint64_t> &H = r->host_aux;
+    std::vector<StitchSeg> dseg;
+    H.assign(256 / 8, 0);
+    {
+        uint8_t *comp = (uint8_t *)H.data();
+        for (int b = 0; b < 256; b++) comp[b] = (uint8_t)b;
+        const char *from = "ACGTUNMRWSYKVHDBacgtunmrwsykvhdb", *to = "TGCAANKYWSRMBDHVtgcaankywsrmbdhv"; /* bin/ntlink_patch_gaps.py:50-53 */
+        for (int j = 0; from[j]; j++) comp[(uint8_t)from[j]] = (uint8_t)to[j];
+    }
+    uint64_t total = 0;
+    for (uint64_t i = 0; i < n_segs; i++) {
+        const ntl_stitch_seg &g = segs[i];
+        const std::string at = "segment " + std::to_string(i) + ": ";
+        if (g.lo > g.hi) return fail(c, NTL_EINVAL, at + "lo " + std::to_string(g.lo) + " is above hi " + std::to_string(g.hi));
+        StitchSeg d = {0, 0, 0};
+        if (g.store == NTL_STITCH_FILL) {
+            if (g.flags) return fail(c, NTL_EINVAL, at + "a fill takes no flags");
+            if (g.rec > 255u) return fail(c, NTL_EINVAL, at + "the fill byte " + std::to_string(g.rec) + " is no byte");
+            d.flags = STITCH_FILL | (g.rec << 8);
+        } else {
+            if (g.store >= n_stores) return fail(c, NTL_EINVAL, at + "store " + std::to_string(g.store) + " out of range (" + std::to_string(n_stores) + " stores)");
+            const ntl_ascii *a = stores[g.store];
+            if (g.rec >= a->off.size() - 1)
+                return fail(c, NTL_EINVAL, at + "record " + std::to_string(g.rec) + " out of range (" + std::to_string(a->off.size() - 1) + " records)");
+            const uint64_t len = a->off[g.rec + 1] - a->off[g.rec];
+            if (g.hi > len) return fail(c, NTL_EINVAL, at + "hi " + std::to_string(g.hi) + " is beyond the record's " + std::to_string(len) + " bytes");
+            if (g.flags & ~(uint32_t)(NTL_STITCH_REVCOMP | NTL_STITCH_LOWER | NTL_STITCH_LOWER_FIRST))
+                return fail(c, NTL_EINVAL, at + "unknown flag bits " + std::to_string(g.flags));
+            d.src = (uint64_t)(uintptr_t)a->bytes.as<uint8_t>() + a->off[g.rec] + g.lo;
+            d.flags = g.flags;
+        }
+        if (g.hi == g.lo) continue; /* nothing to write, and nothing to lower */
+        H.push_back(total);
+        dseg.push_back(d);
+        total += g.hi - g.lo;
+    }
+    H.push_back(total);
+    const uint64_t n = dseg.size();
+    if ((total + STITCH_TILE - 1) / STITCH_TILE >= 0x7FFFFFFFull) return fail(c, NTL_EINVAL, "more output than one stitch call holds");
+    static_assert(sizeof(StitchSeg) == 16, "two words per device segment");
+    H.resize(32 + n + 1 + 2 * n);
+    if (n) memcpy(H.data() + 32 + n + 1, dseg.data(), n * sizeof(StitchSeg));
+    r->total = total;
+    (void)hipSetDevice(c->device);
+    int rc;
+    if ((rc = r->out.alloc(c, (total + 15) / 16 * 16 + 16)) || (rc = r->aux.alloc(c, H.size() * 8))) return rc;
+    if (total) {
+        HIPCHK(c, hipMemcpyAsync(r->aux.p, H.data(), H.size() * 8, hipMemcpyHostToDevice, c->stream));
+        StitchArgs A;
+        A.comp = r->aux.as<uint8_t>();
+        A.off = r->aux.as<uint64_t>() + 32;
+        A.seg = (const StitchSeg *)(r->aux.as<uint64_t>() + 32 + n + 1);
+        A.n = n; A.total = total; A.out = r->out.as<uint8_t>();
+        {
+            ProfSpan span(c, "stitch");
+            hipLaunchKernelGGL(stitch_kernel, dim3((unsigned)((total + STITCH_TILE - 1) / STITCH_TILE)), dim3(STITCH_NT), 0, c->stream, A);
+        }
+        HIPCHK(c, hipGetLastError());
+        if ((r->queued = c->pq.event_get())) HIPCHK(c, hipEventRecord(r->queued, c->stream));
+        else HIPCHK(c, hipStreamSynchronize(c->stream));
+    }
+    *out = r.release();
+    return NTL_OK;
+}
+
+extern "C" uint64_t ntl_stitched_bytes(const ntl_stitched *s) { return s ? s->total : 0; }
+
+/* bytes [lo, hi) of the result into out (page-locked memory: one DMA); waits for them */
+extern "C" int ntl_stitched_copy(const ntl_stitched *s, uint64_t lo, uint64_t hi, char *out)
+{
+    if (!s) return NTL_EINVAL;
+    ntl_ctx *c = s->c;
+    if (lo > hi || hi > s->total) return fail(c, NTL_EINVAL, "range [" + std::to_string(lo) + ", " + std::to_string(hi) + ") outside the result's " + std::to_string(s->total) + " bytes");
+    if (lo == hi) return NTL_OK;
+    if (!out) return NTL_EINVAL;
+    (void)hipSetDevice(c->device);
+    HIPCHK(c, hipMemcpyAsync(out, s->out.as<uint8_t>() + lo, hi - lo, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, main_wait(c));
+    return NTL_OK;
+}
+
+extern "C" void ntl_stitched_destroy(ntl_stitched *s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->c->device);
+    if (s->queued) { (void)hipEventSynchronize(s->queued); s->c->pq.event_put(s->queued); } /* host_aux was the upload's source */
+    delete s;
 }
 
 /* ------------------------------------------------------------------ sketch --------------- */

@@ -43,9 +43,19 @@ instead, ``mask_ranges`` says what every record keeps, and ``gap_cuts_resident``
 full-length records there (Device.batch_mask, ntl_batch_mask, csrc/mask_kernels.h) and go on as the file form does: the same GapCuts,
 the same fields in ``pairs`` and ``scaffolds``, the two files never written.  ``print_masked_sequences`` is the reference's function
 restated over bytes for whoever wants the files; nothing falls back to it.
+
+At the end stand the two functions the stage exists for (print_gap_filled_sequences :533-598 with :668-704, print_agp :600-665) and
+main() (:760-836).  ``output_plan`` walks the path file ONCE and lists what both writers need: per output record its pieces (slices
+of scaffolds and reads, runs of N), the AGP rows, the seven counters of the filling summary and the scaffolds no path names.
+``print_gap_filled_sequences`` turns the pieces into segments of Device.stitch (ntl_stitch, csrc/stitch_kernels.h) over the bytes of
+the scaffolds and the chosen reads, resident as they were read (Resident.ascii), and writes ``args.o`` from page-locked memory;
+``print_agp`` writes ``args.o + ".agp"``; ``patch_gaps(args, dev)`` is main(): no temporary file is written, none is removed.
 """
 import collections
+import copy
+import datetime
 import itertools
+import os
 import re
 
 import numpy as np
@@ -333,10 +343,12 @@ def map_gap_reads(scaffolds_fasta, reads_fasta, k, w, args, dev=None, with_minim
 class Resident:
     """Records resident on the device: ``ids``, ``lengths`` (u32), ``number`` (id -> record number) and ``batch`` (capi.Batch).  With
     keep_ascii also the bytes as they were read, case and IUPAC codes included (``buf``, ``offsets``; ``resident[id]`` is one
-    record's).  Close it, or use it as a context manager, to free the batch."""
+    record's).  With stitchable the same bytes are resident too (``ascii``: capi.Ascii, a source of Device.stitch).  Close it, or use
+    it as a context manager, to free the batch and the bytes."""
 
-    def __init__(self, ids, lengths, batch, buf=None, offsets=None):
+    def __init__(self, ids, lengths, batch, buf=None, offsets=None, ascii=None):
         self.ids, self.lengths, self.batch, self.buf, self.offsets = list(ids), np.ascontiguousarray(lengths, np.uint32), batch, buf, offsets
+        self.ascii = ascii
         self.number = {rid: i for i, rid in enumerate(self.ids)}
         if len(self.number) != len(self.ids):
             raise ValueError("two records with the same id")
@@ -360,6 +372,9 @@ class Resident:
         if self.batch is not None:
             self.batch.close()
             self.batch = None
+        if self.ascii is not None:
+            self.ascii.close()
+            self.ascii = None
 
     def __enter__(self):
         return self
@@ -368,16 +383,17 @@ class Resident:
         self.close()
 
 
-def _resident(dev, ids, seqs, keep_ascii):
+def _resident(dev, ids, seqs, keep_ascii, stitchable=False):
     lens = np.fromiter((len(s) for s in seqs), np.uint64, len(seqs))
     offsets = np.zeros(len(seqs) + 1, np.uint64)
     np.cumsum(lens, out=offsets[1:])
     buf = np.frombuffer(b"".join(seqs), np.uint8)
     batch = dev.batch(buf, offsets)
-    return Resident(ids, lens, batch, buf if keep_ascii else None, offsets if keep_ascii else None)
+    return Resident(ids, lens, batch, buf if keep_ascii else None, offsets if keep_ascii else None,
+                    dev.ascii(buf, offsets) if stitchable else None)
 
 
-def get_gap_fill_reads(reads_filename_list, pairs, args=None, dev=None, keep_ascii=False, max_bases=BATCH_BASES):
+def get_gap_fill_reads(reads_filename_list, pairs, args=None, dev=None, keep_ascii=False, max_bases=BATCH_BASES, stitchable=False):
     """get_gap_fill_reads (:264-273): goes through the read files (FASTA / FASTQ, gzip or not) and keeps the chosen reads of `pairs`
     only -- as ONE resident batch instead of a dict of strings.  A later record with the same id replaces an earlier one, as the
     reference's dict does (and keeps the earlier one's place).  -> Resident.  `args` is not read (the reference takes its thread
@@ -390,19 +406,19 @@ def get_gap_fill_reads(reads_filename_list, pairs, args=None, dev=None, keep_asc
         for i, name in enumerate(ss.names):
             if name in wanted:
                 kept[name] = bytes(ss.buf[off[i]:off[i + 1]])
-    return _resident(dev, list(kept), list(kept.values()), keep_ascii)
+    return _resident(dev, list(kept), list(kept.values()), keep_ascii, stitchable)
 
 
-def resident_scaffolds(path_or_records, dev=None, keep_ascii=False):
+def resident_scaffolds(path_or_records, dev=None, keep_ascii=False, stitchable=False):
     """The scaffolds of ``args.s`` as one resident batch: a FASTA path, or records [(id, sequence as bytes or str)].  -> Resident.
     One batch holds up to 2^32 - 4112 bases."""
     dev = dev or anchor._default_device()
     if isinstance(path_or_records, str):
         ss = seqio.load_all([path_or_records])
         return Resident(ss.names.tolist(), ss.lengths, dev.batch(ss.buf, ss.offsets), ss.buf if keep_ascii else None,
-                        ss.offsets if keep_ascii else None)
+                        ss.offsets if keep_ascii else None, dev.ascii(ss.buf, ss.offsets) if stitchable else None)
     recs = [(rid, seq.encode() if isinstance(seq, str) else bytes(seq)) for rid, seq in path_or_records]
-    return _resident(dev, [rid for rid, _seq in recs], [seq for _rid, seq in recs], keep_ascii)
+    return _resident(dev, [rid for rid, _seq in recs], [seq for _rid, seq in recs], keep_ascii, stitchable)
 
 
 MaskRanges = collections.namedtuple("MaskRanges", "keys scaffold_names scaffold_lo scaffold_hi read_ids read_lo read_hi src_minus tgt_minus")
@@ -531,6 +547,7 @@ class PairInfo:
         self.target_ctg_cut = None
         self.target_read_cut = None
         self.old_anchor_used = False
+        self.chosen_reversed = None  # the chosen read lies on the source the other way round than the path has it (:567, :636)
 
 
 def read_path_file_pairs(path_filename, min_gap_size):
@@ -612,13 +629,14 @@ def choose_gap_reads(pairs, mappings_filename, sequences, args, dev=None, max_by
                     raise ValueError(f"{mappings_filename}: read {rid} supports pairs from two separate groups of lines")
             infos[pair].mapping_reads.add(rid)
             if flags & stop and (best[pair] is None or (anchors, rid) > best[pair][:2]):
-                best[pair] = (anchors, rid, bool(flags & capi.NTL_GAPSEL_NEGATIVE), sc, sr, tc, tr)
+                best[pair] = (anchors, rid, bool(flags & capi.NTL_GAPSEL_NEGATIVE), sc, sr, tc, tr, bool(flags & capi.NTL_GAPSEL_VIA_REVCOMP))
     for (source, target), info, got in zip(pairs, infos, best):
         if got is None:
             continue
         assert not got[2], f"pair {source} {target}, read {got[1]}: a negative distance to a contig end (calculate_est_gap_size)"
         info.chosen_read = got[1]
-        info.source_ctg_cut, info.source_read_cut, info.target_ctg_cut, info.target_read_cut = got[3:]
+        info.source_ctg_cut, info.source_read_cut, info.target_ctg_cut, info.target_read_cut = got[3:7]
+        info.chosen_reversed = got[7]  # found directly: the read has the source's sign; as the reverse-complement pair: the other
 
 
 # The same in plain Python, as the reference has it: the comparison for the tests and for tools/gapmap_bench.py, never a fallback.
@@ -708,8 +726,294 @@ def choose_gap_reads_restated(pairs, mappings_filename, sequences, args):
             assert not negative
             if valid:
                 pair.chosen_read = read_id
+                pair.chosen_reversed = mappings[read_id][source.strip("+-")][2] != source[-1]
                 break
     for (source, target), pair in pairs.items():
         if pair.chosen_read is not None:
             pair.source_ctg_cut, pair.source_read_cut, pair.target_ctg_cut, pair.target_read_cut = \
                 _restated_cuts(source, target, mappings[pair.chosen_read], args.large_k)
+
+
+# ---------------------------------------------------------------- the output (bin/ntlink_patch_gaps.py:20-45, 533-713, 733-836)
+
+STITCH_BYTES = 1 << 30   # output text per Device.stitch call (whole records; a larger record goes alone)
+WRITE_PIECE = 64 << 20   # bytes per copy into page-locked memory and ntl_write_blob
+_COUNTERS = ("num_gaps", "overlap_pts", "small_gaps", "potential_fills", "filled_gaps", "new_anchor_used", "old_anchor_used")
+
+
+class ScaffoldGaps:
+    """A scaffold with the reference's fields (:20-45).  ``seq`` may stay None: the stage keeps the bytes on the device."""
+
+    def __init__(self, seq=None, length=None):
+        self.seq = seq
+        self.length = len(seq) if length is None else int(length)
+        self.five_prime_cut = 0
+        self.three_prime_cut = self.length
+        self.five_prime_trim = 0
+        self.three_prime_trim = self.length
+
+    def get_cut_coordinates(self):
+        return max(self.five_prime_trim, self.five_prime_cut), min(self.three_prime_trim, self.three_prime_cut)
+
+
+def read_trim_coordinates(sequences, args):
+    """read_trim_coordinates (:707-713)"""
+    with open(args.trims, "r") as fin:
+        for line in fin:
+            ctg, start, end = line.strip().split("\t")
+            sequences[ctg].five_prime_trim = int(start)
+            sequences[ctg].three_prime_trim = int(end)
+
+
+OutputPlan = collections.namedtuple("OutputPlan", "records agp counters printed unassigned")
+
+
+def _slice(lo, hi, length):
+    """[lo, hi) as Python's slice of a sequence of `length` takes it (lo, hi >= 0): clamped, empty where they cross"""
+    lo, hi = min(lo, length), min(hi, length)
+    return (lo, hi) if lo < hi else (lo, lo)
+
+
+def output_plan(path_file, pairs, sequences, args):
+    """One walk over the path file for print_gap_filled_sequences (:533-598) and print_agp (:600-665), the two loops restated side by
+    side -- they are not symmetric, see the comments.  pairs: (source, target) -> PairInfo with ``chosen_reversed``; sequences: name ->
+    ScaffoldGaps; args: ``.min_gap`` (already one more than the option, as main() leaves it) and ``.soft_mask``.  -> OutputPlan:
+
+    * records: per line with a tab, in order, (id, pieces) -- a piece is ("scaffold", name, lo, hi, flags), ("read", read id, lo, hi,
+      flags) with lo <= hi and capi.NTL_STITCH_* flags, or ("N", count).  Scaffold slices are clamped to the scaffold; a read's are
+      clamped by whoever knows its length (Python's slice would)
+    * agp: the rows of the .agp file as tuples of its columns, the unassigned scaffolds' last
+    * counters: the seven of print_filling_stats; printed: the scaffolds some path names; unassigned: the others, in order"""
+    records, agp, printed = [], [], set()
+    counters = dict.fromkeys(_COUNTERS, 0)
+    overlap_gap = False  # outlives a line, as in the reference
+    with open(path_file, "r") as fin:
+        for line in fin:
+            start, component_id = 1, 1
+            line = line.strip().split("\t")
+            if len(line) < 2:
+                continue
+            ctg_id, path = line
+            path = path.split(" ")
+            pieces = []
+            for idx, node in enumerate(path):
+                gap_match = _GAP.search(node)
+                if gap_match:
+                    gap_size = int(gap_match.group(1))
+                    counters["num_gaps"] += 1
+                    if gap_size == 1:  # tally_small_gaps (:697-704)
+                        overlap_gap = True
+                        counters["overlap_pts"] += 1
+                    if args.min_gap >= gap_size > 1:
+                        counters["small_gaps"] += 1
+                    gap_size -= 1  # abyss-scaffold's gap is one more
+                    pair = pairs.get((path[idx - 1], path[idx + 1]))
+                    if pair is None:
+                        pieces.append(("N", max(gap_size, 0)))
+                        if gap_size > 0:  # the row is written, and neither it nor a skipped one advances component_id (`continue`, :625-627)
+                            agp.append((ctg_id, start, start + gap_size - 1, component_id, "N", gap_size, "scaffold", "yes", "paired-ends"))
+                            start += gap_size
+                        continue
+                    counters["potential_fills"] += 1
+                    if pair.source_read_cut is None or pair.target_read_cut is None:
+                        pieces.append(("N", max(pair.gap_size, 0)))  # the FASTA takes the pair's size, the AGP the path's (the same number)
+                        agp.append((ctg_id, start, start + gap_size - 1, component_id, "N", gap_size, "scaffold", "yes", "paired-ends"))
+                        start += gap_size
+                    else:
+                        counters["filled_gaps"] += 1
+                        counters["old_anchor_used" if pair.old_anchor_used else "new_anchor_used"] += 1  # tally_anchors (:689-694)
+                        if pair.chosen_reversed:
+                            read_start, read_end, ori = pair.target_read_cut, pair.source_read_cut, "-"
+                        else:
+                            read_start, read_end, ori = pair.source_read_cut, pair.target_read_cut, "+"
+                        flags = (capi.NTL_STITCH_REVCOMP if ori == "-" else 0) | (capi.NTL_STITCH_LOWER if args.soft_mask else 0)
+                        pieces.append(("read", pair.chosen_read, read_start, max(read_start, read_end), flags))
+                        if not read_end >= read_start + 1:
+                            continue  # a fully eroded read: no row, component_id stays
+                        agp.append((ctg_id, start, start + (read_end - read_start) - 1, component_id, "P", pair.chosen_read, read_start + 1,
+                                    read_end, ori))
+                        start += read_end - read_start
+                else:
+                    name = node.strip("+-")
+                    printed.add(name)
+                    scaf_start, scaf_end = sequences[name].get_cut_coordinates()
+                    lo, hi = _slice(scaf_start, scaf_end, sequences[name].length)
+                    flags = capi.NTL_STITCH_REVCOMP if node[-1] == "-" else 0
+                    if overlap_gap:  # cleared even when the piece is empty
+                        flags |= capi.NTL_STITCH_LOWER_FIRST
+                        overlap_gap = False
+                    pieces.append(("scaffold", name, lo, hi, flags))
+                    if not scaf_end >= scaf_start + 1:
+                        continue  # a fully eroded scaffold
+                    agp.append((ctg_id, start, start + (scaf_end - scaf_start) - 1, component_id, "W", name, scaf_start + 1, scaf_end, node[-1]))
+                    start += scaf_end - scaf_start
+                component_id += 1
+            records.append((ctg_id, pieces))
+    unassigned = [name for name in sequences if name not in printed]
+    for name in unassigned:  # the FASTA has the whole untrimmed sequence, the AGP the cut coordinates
+        ctg_start, ctg_end = sequences[name].get_cut_coordinates()
+        agp.append((name, ctg_start + 1, ctg_end, 1, "W", name, ctg_start + 1, ctg_end, "+"))
+    return OutputPlan(records, agp, counters, printed, unassigned)
+
+
+def print_filling_stats(counter, file=None):
+    """print_filling_stats (:668-678)"""
+    out = lambda *a, **kw: print(*a, file=file, **kw)
+    out("\nGap filling summary:")
+    out("Number of detected sequence joins", counter["num_gaps"], sep="\t")
+    out("Number of overlap sequence joins", counter["overlap_pts"], sep="\t")
+    out("Number of gaps smaller than threshold", counter["small_gaps"], sep="\t")
+    out("Number of potentially fillable gaps", counter["potential_fills"], sep="\t")
+    out("Number of filled gaps", counter["filled_gaps"], sep="\t")
+    out("Number of pass 2 anchors used", counter["new_anchor_used"], sep="\t")
+    out("Number of pass 1 anchors used", counter["old_anchor_used"], sep="\t")
+    out()
+
+
+def _record_segments(plan, sequences, scaffolds, reads):
+    """per output record (header bytes, [(store, rec, lo, hi, flags)], bytes of text): stores 0 = scaffolds, 1 = reads, 2 = the headers
+    of the call the record goes to (its `rec` is filled in there)"""
+    fill = capi.NTL_STITCH_FILL
+    for ctg_id, pieces in plan.records:
+        segs, size = [], 0
+        for piece in pieces:
+            if piece[0] == "N":
+                seg = (fill, ord("N"), 0, piece[1], 0)
+            elif piece[0] == "scaffold":
+                seg = (0, scaffolds.number[piece[1]], piece[2], piece[3], piece[4])
+            else:
+                rec = reads.number[piece[1]]
+                lo, hi = _slice(piece[2], piece[3], int(reads.lengths[rec]))
+                seg = (1, rec, lo, hi, piece[4])
+            if seg[3] > seg[2]:
+                segs.append(seg)
+                size += seg[3] - seg[2]
+        header = b">" + ctg_id.encode() + b"\n"
+        yield header, segs, len(header) + size + 1
+    for name in plan.unassigned:
+        header = b">" + name.encode() + b"\n"
+        rec = scaffolds.number[name]
+        length = int(scaffolds.lengths[rec])
+        yield header, [(0, rec, 0, length, 0)] if length else [], len(header) + length + 1
+
+
+def _stitch_calls(records, max_bytes):
+    """whole records per call, at most max_bytes of text each; a larger record goes alone"""
+    call, size = [], 0
+    for rec in records:
+        if call and size + rec[2] > max_bytes:
+            yield call
+            call, size = [], 0
+        call.append(rec)
+        size += rec[2]
+    if call:
+        yield call
+
+
+def print_gap_filled_sequences(pairs, sequences, scaffolds, reads, args, dev=None, max_bytes=STITCH_BYTES, plan=None, stats_file=None):
+    """print_gap_filled_sequences (:533-598): writes ``args.o`` and prints the filling summary.  scaffolds, reads: Resident made with
+    stitchable=True (their bytes are the sources); sequences: name -> ScaffoldGaps with the final cuts and trims.  Per call of
+    Device.stitch whole output records of at most max_bytes of text together; the text comes back in pieces into page-locked memory and
+    goes to the file through ntl_write_blob.  -> the OutputPlan."""
+    dev = dev or anchor._default_device()
+    if scaffolds.ascii is None or reads.ascii is None:
+        raise ValueError("the scaffolds' and the reads' bytes must be resident (stitchable=True)")
+    plan = plan or output_plan(args.path, pairs, sequences, args)
+    newline = (capi.NTL_STITCH_FILL, ord("\n"), 0, 1, 0)
+    fd = os.open(args.o, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+    buf = None
+    try:
+        for call in _stitch_calls(_record_segments(plan, sequences, scaffolds, reads), max_bytes):
+            segs = []
+            for i, (header, rec_segs, _size) in enumerate(call):
+                segs.append((2, i, 0, len(header), 0))
+                segs += rec_segs
+                segs.append(newline)
+            with dev.ascii([header for header, _segs, _size in call]) as headers, \
+                    dev.stitch([scaffolds.ascii, reads.ascii, headers], np.array(segs, capi.STITCH_SEG_DT)) as text:
+                total = text.nbytes
+                if buf is None or len(buf) < min(total, WRITE_PIECE):
+                    dev.pinned_release(buf)
+                    buf = dev.pinned_empty(min(total, WRITE_PIECE))
+                for lo in range(0, total, len(buf)):
+                    hi = min(total, lo + len(buf))
+                    text.copy(lo, hi, buf)
+                    if dev.L.ntl_write_blob(fd, buf.ctypes.data, hi - lo) != 0:
+                        raise OSError(f"{args.o}: write failed")
+    finally:
+        os.close(fd)
+        dev.pinned_release(buf)
+    print_filling_stats(plan.counters, file=stats_file)
+    return plan
+
+
+def print_agp(pairs, sequences, args, plan=None):
+    """print_agp (:600-665): writes ``args.o + ".agp"``"""
+    plan = plan or output_plan(args.path, pairs, sequences, args)
+    with open(args.o + ".agp", "w") as out:
+        for row in plan.agp:
+            out.write("\t".join(str(col) for col in row) + "\n")
+    return plan
+
+
+def print_log_message(message):
+    """:729-731"""
+    print(datetime.datetime.today(), message, flush=True)
+
+
+def print_parameters(args):
+    """print_parameters (:733-758)"""
+    print("Running ntLink gap-filling...\n")
+    print("Parameters:")
+    print("\t--path", args.path)
+    print("\t--mappings", args.mappings)
+    print("\t--trims", args.trims)
+    print("\t-s", args.s)
+    print("\t--reads", args.reads)
+    print()
+    print("\t-z", args.z)
+    print("\t-k", args.k)
+    print("\t-w", args.w)
+    print("\t-t", args.t)
+    print("\t--large_k", args.large_k)
+    print("\t-x", args.x)
+    print("\t--min_gap", args.min_gap)
+    print("\t-o", args.o)
+    if args.verbose:
+        print("\t--verbose")
+    if args.stringent:
+        print("\t--stringent")
+    if args.soft_mask:
+        print("\t--soft_mask")
+    print()
+
+
+def patch_gaps(args, dev=None, max_bytes=STITCH_BYTES):
+    """main() of the reference behind its argument parser (:786-836): the whole gap-filling stage.  args: the reference's namespace
+    (path mappings trims s reads z k w t large_k x min_gap o stringent soft_mask sensitive verbose; it is not changed).  Writes
+    ``args.o`` and ``args.o + ".agp"`` and prints the reference's log lines and the filling summary; the two masked temporary files
+    of the reference are never written.  -> (pairs, sequences, OutputPlan)."""
+    dev = dev or anchor._default_device()
+    args = copy.copy(args)
+    args.min_gap = args.min_gap + 1
+    pairs = read_path_file_pairs(args.path, args.min_gap)
+    print_log_message("Reading scaffolds..")
+    with resident_scaffolds(args.s, dev=dev, stitchable=True) as scaffolds:
+        sequences = {name: ScaffoldGaps(length=length) for name, length in zip(scaffolds.ids, scaffolds.lengths.tolist())}
+        print_log_message("Reading trim coordinates..")
+        read_trim_coordinates(sequences, args)
+        print_log_message("Reading ntLink read mappings..")  # (read block by block while the reads are chosen)
+        print_log_message("Choosing best read..")
+        print_log_message("Finding masking points..")
+        choose_gap_reads(pairs, args.mappings, sequences, args, dev=dev)
+        print_log_message("Collecting reads...")
+        with get_gap_fill_reads(args.reads, pairs, args, dev=dev, stitchable=True) as reads:
+            print_log_message("Mapping long reads..")
+            map_long_reads_resident(pairs, sequences, scaffolds, reads, args, dev=dev)
+            print_log_message("Printing output scaffolds..")
+            plan = output_plan(args.path, pairs, sequences, args)
+            print_gap_filled_sequences(pairs, sequences, scaffolds, reads, args, dev=dev, max_bytes=max_bytes, plan=plan)
+            print_log_message("Printing AGP file..")
+            print_agp(pairs, sequences, args, plan=plan)
+    print_log_message("DONE!")
+    return pairs, sequences, plan
