@@ -372,6 +372,20 @@ uint64_t ntl_mapres_n_pafs(const ntl_mapres *r);
 /* Number of read minimizers found in the index (before any filter): the hit fraction h. */
 uint64_t ntl_mapres_n_index_hits(const ntl_mapres *r);
 int ntl_mapres_download(const ntl_mapres *r, ntl_mapping *maps, ntl_hit *hits, ntl_paf *pafs);
+/* A completed map result made of the caller's records: the counterpart of ntl_sketch_from_host on the map side (no kernel runs, the
+ * three arrays are uploaded), so that ntl_mapres_download and ntl_mapres_format can be given records the mapper would not produce.
+ *   maps[n_maps]            in result order; read / ctg index the name tables later handed to ntl_mapres_format (not checked here)
+ *   hit_slots[n_hit_slots]  the hit array AS THE DEVICE KEEPS IT: mapping m's hits are hit_slots[maps[m].hit_off .. + maps[m].n_hits).
+ *                           The regions ascend with the mapping number and do not overlap; slots in front of the first region,
+ *                           between two regions and behind the last one are unused (the mapper leaves such slots too).
+ *   pafs[n_pafs]            as ntl_mapres_download hands them out
+ * n_hits of the result is the sum of maps[].n_hits; ntl_mapres_download returns the dense restatement (hit_off rewritten to the
+ * running sum of n_hits, the hits gathered from their regions).  The result is complete when the call returns (nothing pending), it
+ * is not grouped (ntl_mapres_grouped_info and ntl_mapres_gap_cuts refuse it with NTL_EINVAL), n_index_hits is 0, and the arrays may
+ * go at once.  NTL_EINVAL with a message: a mapping with n_hits == 0, a region that leaves hit_slots, a region that overlaps the one
+ * before it or lies in front of it, a NULL array with a non-zero count, 2^32 - 256 or more records in one array. */
+int ntl_mapres_from_host(ntl_ctx *ctx, const ntl_mapping *maps, uint64_t n_maps, const ntl_hit *hit_slots, uint64_t n_hit_slots,
+                         const ntl_paf *pafs, uint64_t n_pafs, ntl_mapres **out);
 
 /* Grouped mapping: ntl_index_build + ntl_map_run once per group, on that group's contigs and reads alone, in one device pass -- the
  * gap filler's re-mapping loop (map_long_reads, bin/ntlink_patch_gaps.py:412-442: per gap one read piece against the minimizer dict

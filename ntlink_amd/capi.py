@@ -27,7 +27,7 @@ SYMBOLS = [
     "ntl_sketch_from_host", "ntl_overlap_filter",
     "ntl_index_build", "ntl_index_destroy", "ntl_index_size",
     "ntl_map_run", "ntl_mapres_destroy", "ntl_mapres_n_mappings", "ntl_mapres_n_hits", "ntl_mapres_n_pafs",
-    "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_map_run_grouped", "ntl_mapres_grouped_info", "ntl_mapres_gap_cuts",
+    "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_mapres_from_host", "ntl_map_run_grouped", "ntl_mapres_grouped_info", "ntl_mapres_gap_cuts",
     "ntl_fastx_open", "ntl_fastx_open_range", "ntl_fastx_range", "ntl_fastx_close", "ntl_fastx_error", "ntl_fastx_next", "ntl_fastx_sizes", "ntl_fastx_copy", "ntl_fastx_copy_packed", "ntl_fastx_runs", "ntl_fastx_next_span", "ntl_fastx_parse_span", "ntl_fastx_copy_span", "ntl_fastx_seqs", "ntl_fastx_offsets",
     "ntl_fastx_names", "ntl_fastx_name_offsets", "ntl_write_indexlr", "ntl_write_verbose", "ntl_write_paf",
     "ntl_tsv_open", "ntl_tsv_close", "ntl_tsv_error", "ntl_tsv_next", "ntl_tsv_sizes", "ntl_tsv_copy",
@@ -177,6 +177,7 @@ def load(path=None):
         f.argtypes = [vp]
         f.restype = C.c_uint64
     L.ntl_mapres_download.argtypes = [vp, vp, vp, vp]
+    L.ntl_mapres_from_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp)]
     L.ntl_host_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.ntl_host_free.argtypes = [vp, vp]
     L.ntl_host_free.restype = None
@@ -815,6 +816,16 @@ class Device:
         p = C.c_void_p()
         self._chk(self.L.ntl_map_run(self.ptr, index.ptr, read_sketch.ptr, _ptr(rl, C.c_uint32), C.byref(P),
                                      C.byref(p)))
+        return MapResult(self, p)
+
+    def mapres_from_host(self, maps, hit_slots, pafs):
+        """A completed MapResult of the caller's records (ntl_mapres_from_host, the map side's sketch_from_arrays): maps (MAPPING_DT)
+        whose hit_off index hit_slots (HIT_DT), the hit array as the device keeps it -- regions that ascend with the mapping number,
+        unused slots allowed in front of, between and behind them -- and pafs (PAF_DT).  download() gives the dense restatement."""
+        m = np.ascontiguousarray(maps, MAPPING_DT); h = np.ascontiguousarray(hit_slots, HIT_DT); q = np.ascontiguousarray(pafs, PAF_DT)
+        p = C.c_void_p()
+        self._chk(self.L.ntl_mapres_from_host(self.ptr, m.ctypes.data if len(m) else None, len(m), h.ctypes.data if len(h) else None, len(h),
+                                              q.ctypes.data if len(q) else None, len(q), C.byref(p)))
         return MapResult(self, p)
 
     def map_grouped(self, contig_sketch, ctg_len, ctg_group_off, read_sketch, read_len, read_group_off, k, z=1000, x=0.0, sensitive=False,

@@ -2519,6 +2519,50 @@ extern "C" int ntl_map_run(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *re
     return NTL_OK;
 }
 
+/* A completed result from the caller's records (the map side's ntl_sketch_from_host): no kernel, three uploads.  The hits keep the
+   layout map_gather_kernel leaves -- regions that ascend with the mapping number, unused slots wherever the caller put them -- so that
+   densify and the text kernels see what they see behind the mapper.  Nothing is armed: lz stays as constructed (not pending, no
+   event, no slot, no holds), the result is neither grouped nor gap-shaped and has no map_off. */
+extern "C" int ntl_mapres_from_host(ntl_ctx *c, const ntl_mapping *maps, uint64_t n_maps, const ntl_hit *hit_slots, uint64_t n_hit_slots,
+                                    const ntl_paf *pafs, uint64_t n_pafs, ntl_mapres **out)
+{
+    if (!c || !out) return NTL_EINVAL;
+    *out = nullptr;
+    (void)hipSetDevice(c->device);
+    if ((n_maps && !maps) || (n_hit_slots && !hit_slots) || (n_pafs && !pafs))
+        return fail(c, NTL_EINVAL, "ntl_mapres_from_host: a null array with a non-zero count");
+    if (n_maps >= 0xFFFFFF00ull || n_hit_slots >= 0xFFFFFF00ull || n_pafs >= 0xFFFFFF00ull)
+        return fail(c, NTL_EINVAL, "ntl_mapres_from_host: too many records for one result");
+    uint64_t n_hits = 0, at = 0; /* at: the first slot behind the regions so far */
+    for (uint64_t m = 0; m < n_maps; m++) {
+        const ntl_mapping &M = maps[m];
+        if (!M.n_hits) return fail(c, NTL_EINVAL, "ntl_mapres_from_host: mapping " + std::to_string(m) + " has no hits");
+        if (M.hit_off > n_hit_slots || M.n_hits > n_hit_slots - M.hit_off)
+            return fail(c, NTL_EINVAL, "ntl_mapres_from_host: the hit region of mapping " + std::to_string(m) + " leaves hit_slots");
+        if (M.hit_off < at)
+            return fail(c, NTL_EINVAL, "ntl_mapres_from_host: the hit region of mapping " + std::to_string(m) + " overlaps or lies in front of the one before it");
+        at = M.hit_off + M.n_hits;
+        n_hits += M.n_hits;
+    }
+    static_assert(sizeof(ntl_mapping) == sizeof(MapRec) && sizeof(ntl_hit) == sizeof(HitRec) && sizeof(ntl_paf) == sizeof(PafRec),
+                  "ABI records must match the device records");
+    ntl_mapres *R = new ntl_mapres();
+    R->c = c; R->params = ntl_map_params();
+    R->n_maps = n_maps; R->n_hits = n_hits; R->n_pafs = n_pafs;
+    R->rec_cap = std::max<uint64_t>(n_hit_slots, 1);
+    int rc;
+    if ((rc = R->maps.alloc(c, (n_maps + 1) * sizeof(MapRec))) || (rc = R->hits.alloc(c, (n_hit_slots + 1) * sizeof(HitRec))) ||
+        (rc = R->pafs.alloc(c, (n_pafs + 1) * sizeof(PafRec)))) { mapres_free(R); return rc; }
+    hipError_t e = hipSuccess;
+    if (n_maps) e = hipMemcpyAsync(R->maps.p, maps, n_maps * sizeof(MapRec), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_hit_slots) e = hipMemcpyAsync(R->hits.p, hit_slots, n_hit_slots * sizeof(HitRec), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess && n_pafs) e = hipMemcpyAsync(R->pafs.p, pafs, n_pafs * sizeof(PafRec), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream); /* pageable sources: the caller's arrays are free again */
+    if (e != hipSuccess) { mapres_free(R); return fail(c, NTL_EDEVICE, hipGetErrorString(e)); }
+    *out = R;
+    return NTL_OK;
+}
+
 extern "C" void ntl_mapres_destroy(ntl_mapres *r) { mapres_free(r); }
 extern "C" int ntl_mapres_wait(const ntl_mapres *r) { return r ? mapres_finalize(r) : NTL_EINVAL; }
 extern "C" uint64_t ntl_mapres_n_mappings(const ntl_mapres *r) { return r && mapres_finalize(r) == NTL_OK ? r->n_maps : 0; }

@@ -78,6 +78,42 @@ def load_scenario(name):
     return meta, ctext, rtext, exp
 
 
+def parsed_verbose_arrays(path, ctg_names):
+    """formats.parse_verbose of the file in the layout of formats.read_verbose: (names, map_off, maps, anchors, hits)"""
+    from ntlink_amd import capi, formats
+    number = {name: i for i, name in enumerate(ctg_names)}
+    names, map_off, maps, anchors, hits = [], [0], [], [], []
+    with open(path) as fh:
+        for rid, entries in formats.parse_verbose(fh, with_anchors=True):
+            for ctg, hl, anc in entries:
+                maps.append((len(names), number.get(ctg, capi.NO_CTG), len(hl), 0, len(hits)))
+                anchors.append(anc)
+                hits += [(c, r, cs, rs, (0, 0)) for c, cs, r, rs in hl]
+            names.append(rid)
+            map_off.append(len(maps))
+    return names, np.array(map_off, np.uint32), np.array(maps, capi.MAPPING_DT), np.array(anchors, np.uint32), np.array(hits, capi.HIT_DT)
+
+
+def assert_reader_blocks(blocks, want):
+    """the VerboseBlocks of formats.read_verbose over a file, one after the other == parsed_verbose_arrays of that file: in every block
+    the reads, the mappings and the hits count from 0"""
+    names, reads, maps_before, hits_before = [], 0, 0, 0
+    for b in blocks:
+        n = len(b.names)
+        assert n and b.map_off[0] == 0 and int(b.map_off[-1]) == len(b.maps) == len(b.anchors)
+        lo, hi = maps_before, maps_before + len(b.maps)
+        assert (b.map_off.astype(np.int64) + maps_before == want[1][reads:reads + n + 1]).all()
+        for f in ("ctg", "n_hits"):
+            assert (b.maps[f] == want[2][f][lo:hi]).all(), f
+        assert (b.maps["read"].astype(np.int64) + reads == want[2]["read"][lo:hi]).all()
+        assert (b.maps["hit_off"].astype(np.int64) + hits_before == want[2]["hit_off"][lo:hi]).all(), "dense, from 0 in every block"
+        assert (b.anchors == want[3][lo:hi]).all()
+        assert b.hits.tobytes() == want[4][hits_before:hits_before + len(b.hits)].tobytes()
+        names += b.names.tolist()
+        reads, maps_before, hits_before = reads + n, hi, hits_before + len(b.hits)
+    assert names == want[0] and maps_before == len(want[2]) and hits_before == len(want[4])
+
+
 def write_bgzf(path, data, block=0xFF00, level=6):
     """`bgzip` without htslib: gzip members of at most `block` bytes of text, each with the BC extra field that holds its
     compressed size, and the empty EOF member bgzip appends."""

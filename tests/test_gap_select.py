@@ -23,6 +23,7 @@ import types
 import numpy as np
 import pytest
 
+from helpers import assert_reader_blocks, parsed_verbose_arrays
 from ntlink_amd import capi, formats, gapfill
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -206,21 +207,6 @@ def check_random(dev, tmp_path):
 
 # ---------------------------------------------------------------- c. the reader
 
-def _parsed_arrays(path, ctg_names):
-    """formats.parse_verbose of the file in the reader's layout"""
-    number = {name: i for i, name in enumerate(ctg_names)}
-    names, map_off, maps, anchors, hits = [], [0], [], [], []
-    with open(path) as fh:
-        for rid, entries in formats.parse_verbose(fh, with_anchors=True):
-            for ctg, hl, anc in entries:
-                maps.append((len(names), number.get(ctg, capi.NO_CTG), len(hl), 0, len(hits)))
-                anchors.append(anc)
-                hits += [(c, r, cs, rs, (0, 0)) for c, cs, r, rs in hl]
-            names.append(rid)
-            map_off.append(len(maps))
-    return names, np.array(map_off, np.uint32), np.array(maps, capi.MAPPING_DT), np.array(anchors, np.uint32), np.array(hits, capi.HIT_DT)
-
-
 def check_reader(lib_path, tmp_path, monkeypatch):
     doc = golden()
     files = [(_write(tmp_path, "g.tsv", doc["verbose"]), sorted(doc["lengths"])[::2]),
@@ -230,25 +216,11 @@ def check_reader(lib_path, tmp_path, monkeypatch):
         if threads_env:
             monkeypatch.setenv("NTL_IO_MIN_CHUNK", threads_env)
         for path, ctg_names in files:
-            want = _parsed_arrays(path, ctg_names)
+            want = parsed_verbose_arrays(path, ctg_names)
             for max_bytes in (0, SMALL_BLOCK):
                 blocks = list(formats.read_verbose(path, ctg_names, max_bytes=max_bytes, lib_path=lib_path))
                 assert len(blocks) == 1 if not max_bytes else len(blocks) > 20
-                names, reads, maps_before, hits_before = [], 0, 0, 0
-                for b in blocks:
-                    n = len(b.names)
-                    assert n and b.map_off[0] == 0 and int(b.map_off[-1]) == len(b.maps) == len(b.anchors)
-                    lo, hi = maps_before, maps_before + len(b.maps)
-                    assert (b.map_off.astype(np.int64) + maps_before == want[1][reads:reads + n + 1]).all()
-                    for f in ("ctg", "n_hits"):
-                        assert (b.maps[f] == want[2][f][lo:hi]).all(), f
-                    assert (b.maps["read"].astype(np.int64) + reads == want[2]["read"][lo:hi]).all()
-                    assert (b.maps["hit_off"].astype(np.int64) + hits_before == want[2]["hit_off"][lo:hi]).all(), "dense, from 0 in every block"
-                    assert (b.anchors == want[3][lo:hi]).all()
-                    assert b.hits.tobytes() == want[4][hits_before:hits_before + len(b.hits)].tobytes()
-                    names += b.names.tolist()
-                    reads, maps_before, hits_before = reads + n, hi, hits_before + len(b.hits)
-                assert names == want[0] and maps_before == len(want[2]) and hits_before == len(want[4])
+                assert_reader_blocks(blocks, want)
     assert (want[2]["ctg"] == capi.NO_CTG).all()
     # the same id again further on is another read; consecutive lines of one id stay together whatever the block size
     path = _write(tmp_path, "again.tsv", "a\tc\t1\t1:+_2:+\nb\tc\t1\t1:+_2:+\na\tc\t1\t1:+_2:+\n" + "long\tc\t1\t1:+_2:+\n" * 200)
