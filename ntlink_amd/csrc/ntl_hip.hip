@@ -2273,151 +2273,164 @@ extern "C" uint64_t ntl_index_size(const ntl_index *ix)
 /* ------------------------------------------------------------------ map ------------------ */
 
 static_assert(sizeof(MapSums) <= sizeof(PinSlot), "the sums must fit a page-locked slot (map_kernels.h)");
+static_assert(sizeof(ntl_mapping) == sizeof(MapRec) && sizeof(ntl_hit) == sizeof(HitRec) && sizeof(ntl_paf) == sizeof(PafRec),
+              "ABI records must match the device records"); /* uploads, downloads and the gap reader copy them as they are */
 
+/* Made by mapres_new only: a result of ntl_mapres_from_host is these defaults (nothing armed, no lookup, not grouped) plus its records */
 struct ntl_mapres {
     ntl_ctx *c;
+    const ntl_map_params params;
+    ntl_mapres(ntl_ctx *ctx, const ntl_map_params &p) : c(ctx), params(p) {}
     mutable uint64_t n_maps = 0, n_hits = 0, n_pafs = 0, n_index_hits = 0;
     mutable DevBuf maps, pafs;       /* dense, read order; sized from the sketch's capacity, filled to n_* */
     mutable DevBuf hits;             /* per-read regions (read r's hits from mx_off[r] on); maps[].hit_off points into them */
     mutable DevBuf maps_dense, hits_dense, hit_doff; /* made on demand: the dense copy ntl_mapres_download hands out; u32[n_maps + 1] dense offsets */
     mutable bool dense_made = false, doff_made = false;
-    mutable Pending lz;                 /* lazy completion (pending.h); holds[0]: the index, holds[1]: the batch whose lengths the kernels read */
-    const ntl_sketch *reads = nullptr;  /* held (refs) while pending */
-    uint64_t reads_gen = 0;             /* generation of the sketch the kernels were queued on */
-    ntl_map_params params;
+    uint64_t n_reads = 0, rec_cap = 0;  /* reads of the sketch; records `maps`, `hits` and `pafs` hold */
+    mutable Pending lz;                 /* lazy completion (pending.h); holds[0]: the lookup's source (`ix`, or a grouped result's contig sketch), holds[1]: the batch whose lengths the kernels read */
+    /* what map_enqueue queues from, the first time and -- mapres_finalize -- the second */
+    const ntl_index *ix = nullptr;      /* the index of the lookup (ntl_map_run only); alive while lz.holds[0] is */
+    const ntl_sketch *reads = nullptr; uint64_t reads_gen = 0; /* held (refs) while pending; its generation when the kernels were queued */
     std::shared_ptr<std::atomic<float>> hitf; /* the index's hit fraction (the index itself may be gone when this completes) */
     DevBuf rlen_own;                    /* read lengths uploaded by this call (sketches that did not come from a batch) */
     const uint32_t *d_rlen = nullptr;   /* the read lengths the kernels read: rlen_own, or the batch's own (d_seq_len; lz holds the batch) */
-    /* ntl_map_run_grouped: no index; lz.holds[0] is the CONTIG SKETCH (the lookup reads its records), the contig lengths are the result's own */
-    bool grouped = false;
+    /* ntl_map_run_grouped only: no index -- the lookup reads the records of the contig sketch -- and contig lengths of the result's own */
+    bool grouped = false, gap_shaped = false; /* gap_shaped: group g is "contigs 2g and 2g + 1, read g" (ntl_mapres_gap_cuts) */
     ntl_grouped_info ginfo = {};
     DevBuf ctg_len_own;
-    /* for ntl_mapres_gap_cuts: the scans map_enqueue made for its gather (the first third: u32[n_reads + 1], first mapping of every
-       read), kept instead of freed; the records `maps` and `hits` hold; whether group g is "contigs 2g and 2g + 1, read g" */
-    mutable DevBuf map_off;
-    uint64_t n_reads = 0, rec_cap = 0;
-    bool gap_shaped = false;
+    mutable DevBuf map_off;             /* the gather's scans, kept for ntl_mapres_gap_cuts: the first third, u32[n_reads + 1], first mapping of every read */
 };
 
-/* what map_enqueue queues in place of the index lookup for a grouped result (group_kernels.h) */
-struct GroupJob {
-    GroupArgs A;               /* cand, rpos, nfound and err are map_enqueue's to fill in */
-    const uint32_t *d_ctg_len; /* MapArgs::ctg_len: the result's own copy */
-    unsigned grid;
-};
+/* what map_lookup_stage queues in place of the index lookup for a grouped result (group_kernels.h); it fills in cand, rpos, nfound and err */
+struct GroupJob { GroupArgs A; unsigned grid; };
 
-/* Queues the lookup (when the sketch does not carry candidates), the map kernels, the offset scans and the gather on MAIN.
- * Nothing waits: the three totals, the hit count and the invariant flag land in the result's page-locked slot. */
-static int map_enqueue(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *reads, const uint32_t *d_rlen, ntl_mapres *R,
-                       const GroupJob *gj = nullptr)
-{
-    const uint64_t nreads = reads->nseq;
-    const bool have_cand = !gj && reads->cand_gen == ix->gen && reads->cand.p != nullptr;
-    if (reads->no_records && !have_cand) return fail(c, NTL_EINVAL, "a sketch made by ntl_sketch_run_for_map maps against the index it was made for only");
-    if (!have_cand) { /* the lookup pass runs over the records: their number sizes its grid */
-        if (int frc = sketch_finalize(reads)) return frc;
-    }
-    const uint64_t nmx = reads->lz.pending ? reads->cap : reads->count;
-    const ntl_map_params *params = &R->params;
-    int rc;
-    hipStream_t ms = c->stream;
+/* What one map_enqueue holds between its stages (SketchWork is the model).  Every temporary lives here and not in a stage: the blocks
+ * return to the context's cache when map_enqueue ends, behind every kernel of this work on MAIN. */
+struct MapWork {
+    bool have_cand;            /* the sketch carries this index's candidates: no lookup */
+    uint64_t nreads, nmx, cap; /* cap: records the arrays hold (nmx, at least 1) */
     DevBuf cand, rpos, smaps, spafs, n3, off3_own, scr, over;
-    DevBuf &off3 = gj ? R->map_off : off3_own; /* a grouped result keeps its offsets (ntl_mapres_gap_cuts) */
-    R->dense_made = R->doff_made = false;
-    const uint64_t cap = nmx ? nmx : 1;
-    R->n_reads = nreads; R->rec_cap = cap;
-    if ((!have_cand && ((rc = cand.alloc(c, cap * sizeof(Cand))) || (rc = rpos.alloc(c, cap * 4)))) ||
-        (rc = smaps.alloc(c, cap * sizeof(MapRec))) ||
-        (rc = spafs.alloc(c, cap * sizeof(PafRec))) || (rc = n3.alloc(c, 3 * (nreads + 1) * 4)) ||
-        (rc = off3.alloc(c, 3 * (nreads + 1) * 4)) || (rc = scr.alloc(c, (uint64_t)(MAP_NHA + MAP_NRA) * cap * 4)) ||
-        (rc = over.alloc(c, (nreads + 1) * 4)) ||
-        (rc = R->maps.alloc(c, cap * sizeof(MapRec))) || (rc = R->hits.alloc(c, cap * sizeof(HitRec))) ||
-        (rc = R->pafs.alloc(c, cap * sizeof(PafRec)))) return rc;
+    DevBuf *off3;              /* off3_own; a grouped result keeps its offsets: R->map_off (ntl_mapres_gap_cuts) */
+    MapSums *dsums;            /* the result's entry of the per-slot device array (map_prepare) */
+    MapArgs A;
+};
+
+/* The temporaries, the result's arrays and the kernels' arguments, from R->ix (a grouped result has none), R->reads, R->d_rlen, R->params */
+static int map_prepare(ntl_ctx *c, ntl_mapres *R, MapWork &W)
+{
+    const ntl_sketch *reads = R->reads;
+    int rc;
+    W.have_cand = R->ix && reads->cand_gen == R->ix->gen && reads->cand.p != nullptr;
+    if (reads->no_records && !W.have_cand) return fail(c, NTL_EINVAL, "a sketch made by ntl_sketch_run_for_map maps against the index it was made for only");
+    if (!W.have_cand && (rc = sketch_finalize(reads))) return rc; /* the lookup pass runs over the records: their number sizes its grid */
+    const uint64_t nreads = W.nreads = reads->nseq;
+    W.nmx = reads->lz.pending ? reads->cap : reads->count;
+    const uint64_t cap = W.cap = W.nmx ? W.nmx : 1;
+    W.off3 = R->grouped ? &R->map_off : &W.off3_own;
+    R->dense_made = R->doff_made = false; R->n_reads = nreads; R->rec_cap = cap;
+    if ((!W.have_cand && ((rc = W.cand.alloc(c, cap * sizeof(Cand))) || (rc = W.rpos.alloc(c, cap * 4)))) || (rc = W.smaps.alloc(c, cap * sizeof(MapRec))) ||
+        (rc = W.spafs.alloc(c, cap * sizeof(PafRec))) || (rc = W.n3.alloc(c, 3 * (nreads + 1) * 4)) || (rc = W.off3->alloc(c, 3 * (nreads + 1) * 4)) ||
+        (rc = W.scr.alloc(c, (uint64_t)(MAP_NHA + MAP_NRA) * cap * 4)) || (rc = W.over.alloc(c, (nreads + 1) * 4)) ||
+        (rc = R->maps.alloc(c, cap * sizeof(MapRec))) || (rc = R->hits.alloc(c, cap * sizeof(HitRec))) || (rc = R->pafs.alloc(c, cap * sizeof(PafRec)))) return rc;
     /* The sums: the result's entry of the per-slot device array.  It is zero whenever the slot is free -- map_gather_kernel, the last
        kernel of this work, hands the sums to the slot and leaves the entry zero; the slot is recycled only after R->lz.done, behind it
        (or, on the error paths, after pending_abort zeroed it) -- and every kernel that adds to it runs on MAIN behind the gather of the slot's
        previous holder.  The lookup's count of a sketch made for this index stays where the lookup left it (SketchSums::nfound). */
-    MapSums *dsums = (MapSums *)c->pq.slot_dsums(R->lz.slot);
-    if (ix && ix->c != c && ix->built) HIPCHK(c, hipStreamWaitEvent(ms, ix->built, 0));
-    if (!have_cand) {
-        ProfSpan sp(c, "probe");
-        if (gj) { /* every read in the contigs of its own group: tables built, used and dropped by one kernel */
-            if (nmx) {
-                GroupArgs G = gj->A;
-                G.cand = cand.as<Cand>(); G.rpos = rpos.as<uint32_t>(); G.nfound = &dsums->nfound; G.err = &dsums->err;
-                hipLaunchKernelGGL(group_probe_kernel, dim3(gj->grid), dim3(GROUP_NT), 0, ms, G);
-            }
-        } else if (nmx) {
-            const dim3 grid((unsigned)std::min<uint64_t>((nmx + 256 * PROBE_U - 1) / (256 * PROBE_U), 4096));
-            /* tags first unless the previous batch on this index found more than half of its minimizers (same result either way) */
-            if (ix->hit_fraction->load(std::memory_order_relaxed) <= 0.5f)
-                hipLaunchKernelGGL(probe_kernel<true>, grid, dim3(256), 0, ms,
-                                   (const MxRecord *)reads->records.as<MxRecord>(), nmx, (const IndexSlot *)ix->slots.as<IndexSlot>(),
-                                   ix->bits, (const IndexSpecial *)ix->special.as<IndexSpecial>(), cand.as<Cand>(), rpos.as<uint32_t>(),
-                                   &dsums->nfound, (const uint8_t *)ix->tags.as<uint8_t>());
-            else
-                hipLaunchKernelGGL(probe_kernel<false>, grid, dim3(256), 0, ms,
-                                   (const MxRecord *)reads->records.as<MxRecord>(), nmx, (const IndexSlot *)ix->slots.as<IndexSlot>(),
-                                   ix->bits, (const IndexSpecial *)ix->special.as<IndexSpecial>(), cand.as<Cand>(), rpos.as<uint32_t>(),
-                                   &dsums->nfound, (const uint8_t *)ix->tags.as<uint8_t>());
-        }
-        HIPCHK(c, hipGetLastError());
-    }
-    MapArgs A;
-    A.mx_off = reads->mx_off.as<uint32_t>();
-    A.rpos = have_cand ? reads->rpos.as<uint32_t>() : rpos.as<uint32_t>();
-    A.cand = have_cand ? reads->cand.as<Cand>() : cand.as<Cand>();
-    A.read_len = d_rlen; A.ctg_len = gj ? gj->d_ctg_len : ix->ctg_len.as<uint32_t>(); A.nreads = (uint32_t)nreads;
-    A.P.k = params->k; A.P.z = params->z; A.P.x = params->x; A.P.sensitive = params->sensitive;
-    A.P.repeat_filter = params->repeat_filter;
-    A.maps = smaps.as<MapRec>(); A.hits = R->hits.as<HitRec>(); A.pafs = spafs.as<PafRec>();
-    A.n_maps = n3.as<uint32_t>(); A.n_hits = A.n_maps + (nreads + 1); A.n_pafs = A.n_hits + (nreads + 1);
-    A.scr = scr.as<uint32_t>(); A.scr_stride = cap; A.err = &dsums->err;
-    A.over_list = over.as<uint32_t>(); A.over_count = &dsums->n_over;
+    MapSums *dsums = W.dsums = (MapSums *)c->pq.slot_dsums(R->lz.slot);
+    MapArgs &A = W.A;
+    A.mx_off = reads->mx_off.as<uint32_t>(); A.nreads = (uint32_t)nreads;
+    A.rpos = W.have_cand ? reads->rpos.as<uint32_t>() : W.rpos.as<uint32_t>();
+    A.cand = W.have_cand ? reads->cand.as<Cand>() : W.cand.as<Cand>();
+    A.read_len = R->d_rlen; A.ctg_len = R->grouped ? R->ctg_len_own.as<uint32_t>() : R->ix->ctg_len.as<uint32_t>();
+    A.P.k = R->params.k; A.P.z = R->params.z; A.P.x = R->params.x; A.P.sensitive = R->params.sensitive; A.P.repeat_filter = R->params.repeat_filter;
+    A.maps = W.smaps.as<MapRec>(); A.hits = R->hits.as<HitRec>(); A.pafs = W.spafs.as<PafRec>();
+    A.n_maps = W.n3.as<uint32_t>(); A.n_hits = A.n_maps + (nreads + 1); A.n_pafs = A.n_hits + (nreads + 1);
+    A.scr = W.scr.as<uint32_t>(); A.scr_stride = cap; A.err = &dsums->err; A.over_list = W.over.as<uint32_t>(); A.over_count = &dsums->n_over;
     /* a sketch whose count is not known yet may have overflowed its arrays: the kernels look at its total and leave it alone */
     A.mx_total = reads->lz.pending ? &reads->sums.as<SketchSums>()->total_mx : nullptr;
     A.mx_cap = (uint32_t)std::min<uint64_t>(reads->cap, 0xFFFFFFFFull);
-    if (nreads) {
-        {
-            ProfSpan sp(c, "map");
-            /* reads by size class, each class with the LDS staging that fits it; resident-size grids (28 / 14 / 8 wavefronts
-               per CU fit) looping over all reads, 64 at a time */
-            const uint64_t groups = (nreads + MAP_GROUP - 1) / MAP_GROUP;
-            uint64_t g0 = 4 * 7168, g1 = 4 * 3584, g2 = 4 * 2048;
-            if (const char *e = getenv("NTL_MAP_WAVES_PER_CU")) { /* tuning: a bounded number of resident wavefronts beside the window stage */
-                const uint64_t cap = (uint64_t)std::max(1, atoi(e)) * (uint64_t)std::max(1, c->n_cu);
-                g0 = std::min(g0, cap); g1 = std::min(g1, cap); g2 = std::min(g2, cap);
-            }
-            hipLaunchKernelGGL((map_kernel<256, 64, 0>), dim3((unsigned)std::min<uint64_t>(groups, g0)), dim3(MAP_NT), 0, ms, A);
-            hipLaunchKernelGGL((map_kernel<512, 128, 1>), dim3((unsigned)std::min<uint64_t>(groups, g1)), dim3(MAP_NT), 0, ms, A);
-            hipLaunchKernelGGL((map_kernel<1024, 128, 2>), dim3((unsigned)std::min<uint64_t>(groups, g2)), dim3(MAP_NT), 0, ms, A);
-            /* reads with more hits / runs than the largest staging holds (rare): same code on global scratch */
-            hipLaunchKernelGGL(map_overflow_kernel, dim3((unsigned)std::min<uint64_t>(nreads, 8192)), dim3(MAP_NT), 0, ms, A); /* no LDS: 32 wavefronts per CU resident */
-            HIPCHK(c, hipGetLastError());
-        }
-        ProfSpan sp(c, "compact");
-        uint32_t *o = off3.as<uint32_t>();
-        if ((rc = device_scan(c, n3.as<uint32_t>(), o, nreads, nullptr, 3, dsums->tot))) return rc;
-        MapSumsOut O;
-        O.sums = dsums;
-        O.nfound = have_cand ? &reads->sums.as<SketchSums>()->nfound : &dsums->nfound;
-        O.slot = (unsigned long long *)c->pq.slot_dev(R->lz.slot);
-        /* the sketch's own hit count, if nothing has copied it yet: its event moves behind this kernel (sketch_finalize waits for it) */
-        O.sk_nfound = nullptr;
-        if (have_cand && reads->lz.pending && reads->nfound_owed) O.sk_nfound = &((SketchSums *)c->pq.slot_dev(reads->lz.slot))->nfound;
-        hipLaunchKernelGGL(map_gather_kernel, dim3((unsigned)((nreads + GATHER_NT - 1) / GATHER_NT)), dim3(GATHER_NT), 0, ms, A, (const uint32_t *)o,
-                           (const uint32_t *)(o + 2 * (nreads + 1)), R->maps.as<MapRec>(), R->pafs.as<PafRec>(), O);
-        HIPCHK(c, hipGetLastError());
-        if (O.sk_nfound) {
-            HIPCHK(c, hipEventRecord(reads->lz.done, ms));
-            reads->nfound_owed = false;
-        }
-    }
-    /* (no reads: no kernel, and the slot keeps the zeros slot_get left in it) */
-    HIPCHK(c, hipEventRecord(R->lz.done, ms));
-    R->lz.pending = true;
-    R->reads_gen = reads->gen;
     return NTL_OK;
+}
+
+/* The lookup, unless the sketch carries its candidates: the index probe, or gj's probe of every read in its own group's contigs (one kernel builds, uses and drops the tables) */
+static int map_lookup_stage(ntl_ctx *c, const ntl_mapres *R, const GroupJob *gj, MapWork &W)
+{
+    const ntl_index *ix = R->ix;
+    hipStream_t ms = c->stream;
+    if (ix && ix->c != c && ix->built) HIPCHK(c, hipStreamWaitEvent(ms, ix->built, 0));
+    if (W.have_cand) return NTL_OK;
+    ProfSpan sp(c, "probe");
+    if (gj && W.nmx) {
+        GroupArgs G = gj->A;
+        G.cand = W.cand.as<Cand>(); G.rpos = W.rpos.as<uint32_t>(); G.nfound = &W.dsums->nfound; G.err = &W.dsums->err;
+        hipLaunchKernelGGL(group_probe_kernel, dim3(gj->grid), dim3(GROUP_NT), 0, ms, G);
+    } else if (W.nmx) {
+        const dim3 grid((unsigned)std::min<uint64_t>((W.nmx + 256 * PROBE_U - 1) / (256 * PROBE_U), 4096));
+        /* tags first unless the previous batch on this index found more than half of its minimizers (same result either way) */
+        const auto probe = ix->hit_fraction->load(std::memory_order_relaxed) <= 0.5f ? probe_kernel<true> : probe_kernel<false>;
+        hipLaunchKernelGGL(probe, grid, dim3(256), 0, ms, (const MxRecord *)R->reads->records.as<MxRecord>(), W.nmx,
+                           (const IndexSlot *)ix->slots.as<IndexSlot>(), ix->bits, (const IndexSpecial *)ix->special.as<IndexSpecial>(),
+                           W.cand.as<Cand>(), W.rpos.as<uint32_t>(), &W.dsums->nfound, (const uint8_t *)ix->tags.as<uint8_t>());
+    }
+    HIPCHK(c, hipGetLastError());
+    return NTL_OK;
+}
+
+/* Reads by size class, each class with the LDS staging that fits it; resident-size grids (28 / 14 / 8 wavefronts per CU fit) looping
+   over all reads, 64 at a time */
+static int map_kernels_stage(ntl_ctx *c, const MapWork &W)
+{
+    hipStream_t ms = c->stream;
+    ProfSpan sp(c, "map");
+    const uint64_t groups = (W.nreads + MAP_GROUP - 1) / MAP_GROUP;
+    uint64_t g0 = 4 * 7168, g1 = 4 * 3584, g2 = 4 * 2048;
+    if (const char *e = getenv("NTL_MAP_WAVES_PER_CU")) { /* tuning: a bounded number of resident wavefronts beside the window stage */
+        const uint64_t resident = (uint64_t)std::max(1, atoi(e)) * (uint64_t)std::max(1, c->n_cu);
+        g0 = std::min(g0, resident); g1 = std::min(g1, resident); g2 = std::min(g2, resident);
+    }
+    hipLaunchKernelGGL((map_kernel<256, 64, 0>), dim3((unsigned)std::min<uint64_t>(groups, g0)), dim3(MAP_NT), 0, ms, W.A);
+    hipLaunchKernelGGL((map_kernel<512, 128, 1>), dim3((unsigned)std::min<uint64_t>(groups, g1)), dim3(MAP_NT), 0, ms, W.A);
+    hipLaunchKernelGGL((map_kernel<1024, 128, 2>), dim3((unsigned)std::min<uint64_t>(groups, g2)), dim3(MAP_NT), 0, ms, W.A);
+    /* reads with more hits / runs than the largest staging holds (rare): same code on global scratch */
+    hipLaunchKernelGGL(map_overflow_kernel, dim3((unsigned)std::min<uint64_t>(W.nreads, 8192)), dim3(MAP_NT), 0, ms, W.A); /* no LDS: 32 wavefronts per CU resident */
+    HIPCHK(c, hipGetLastError());
+    return NTL_OK;
+}
+
+/* The three offset scans and the gather, whose first lane hands the sums to the result's slot */
+static int map_gather_stage(ntl_ctx *c, ntl_mapres *R, MapWork &W)
+{
+    const ntl_sketch *reads = R->reads;
+    const uint64_t nreads = W.nreads;
+    ProfSpan sp(c, "compact");
+    uint32_t *o = W.off3->as<uint32_t>();
+    if (int rc = device_scan(c, W.n3.as<uint32_t>(), o, nreads, nullptr, 3, W.dsums->tot)) return rc;
+    MapSumsOut O;
+    O.sums = W.dsums; O.slot = (unsigned long long *)c->pq.slot_dev(R->lz.slot);
+    O.nfound = W.have_cand ? &reads->sums.as<SketchSums>()->nfound : &W.dsums->nfound;
+    /* the sketch's own hit count, if nothing has copied it yet: its event moves behind this kernel (sketch_finalize waits for it) */
+    const bool owed = W.have_cand && reads->lz.pending && reads->nfound_owed;
+    O.sk_nfound = owed ? &((SketchSums *)c->pq.slot_dev(reads->lz.slot))->nfound : nullptr;
+    hipLaunchKernelGGL(map_gather_kernel, dim3((unsigned)((nreads + GATHER_NT - 1) / GATHER_NT)), dim3(GATHER_NT), 0, c->stream, W.A, (const uint32_t *)o,
+                       (const uint32_t *)(o + 2 * (nreads + 1)), R->maps.as<MapRec>(), R->pafs.as<PafRec>(), O);
+    HIPCHK(c, hipGetLastError());
+    if (owed) { HIPCHK(c, hipEventRecord(reads->lz.done, c->stream)); reads->nfound_owed = false; }
+    return NTL_OK;
+}
+
+/* Queues the lookup (when the sketch does not carry candidates), the map kernels, the offset scans and the gather on MAIN, from the result's
+ * own fields (and gj for a grouped one).  Nothing waits: the three totals, the hit count and the invariant flag land in its page-locked slot. */
+static int map_enqueue(ntl_ctx *c, ntl_mapres *R, const GroupJob *gj = nullptr)
+{
+    MapWork W;
+    int rc;
+    if ((rc = map_prepare(c, R, W)) || (rc = map_lookup_stage(c, R, gj, W))) return rc;
+    /* (no reads: no kernel, and the slot keeps the zeros slot_get left in it) */
+    if (W.nreads && ((rc = map_kernels_stage(c, W)) || (rc = map_gather_stage(c, R, W)))) return rc;
+    HIPCHK(c, hipEventRecord(R->lz.done, c->stream));
+    R->lz.pending = true;
+    R->reads_gen = R->reads->gen;
+    return NTL_OK; /* (W's temporaries return to the context's cache here) */
 }
 
 /* The check of a map result, completed or destroyed before anybody asked: the invariant flag, and the batch's hit fraction for the
@@ -2439,6 +2452,31 @@ static void mapres_free(ntl_mapres *R)
     delete R;
 }
 
+/* The one way to make a result: whatever path drops the handle gives back event, slot, holds and the sketch (mapres_free) */
+struct MapResFree { void operator()(ntl_mapres *R) const { mapres_free(R); } };
+typedef std::unique_ptr<ntl_mapres, MapResFree> MapResPtr;
+static MapResPtr mapres_new(ntl_ctx *c, const ntl_map_params &params) { return MapResPtr(new ntl_mapres(c, params)); }
+
+/* The one error exit of the calls that make a result.  `queued`: from the call's first launch or async copy on, every exit drains the
+   device and scrubs the slot's device sums (pending_abort) before an armed result lets go of what the queued work reads; before that none does. */
+static int mapres_fail(MapResPtr &R, int rc, bool queued)
+{
+    if (queued && R->lz.slot) pending_abort(R->c, R->lz, rc, true);
+    R.reset();
+    return rc;
+}
+
+/* The lengths a call brings along, into the result's own arrays: rlen_own, which the kernels then read, and a grouped result's
+   ctg_len_own.  wait: the source is pageable and the caller's array must be free again (a caller that waits on MAIN later passes false). */
+static hipError_t mapres_upload_lengths(ntl_mapres *R, const uint32_t *read_len, uint64_t nreads, bool wait, const uint32_t *ctg_len = nullptr, uint64_t n_ctg = 0)
+{
+    hipError_t e = n_ctg ? hipMemcpyAsync(R->ctg_len_own.p, ctg_len, n_ctg * 4, hipMemcpyHostToDevice, R->c->stream) : hipSuccess;
+    if (e == hipSuccess && nreads) e = hipMemcpyAsync(R->rlen_own.p, read_len, nreads * 4, hipMemcpyHostToDevice, R->c->stream);
+    if (e == hipSuccess && nreads && wait) e = hipStreamSynchronize(R->c->stream);
+    R->d_rlen = R->rlen_own.as<uint32_t>();
+    return e;
+}
+
 /* Completes a map result: the sketch first (it may have to be made again with larger arrays -- then the map kernels ran on
  * nothing and are queued again), then this call's totals. */
 static int mapres_finalize(const ntl_mapres *cR)
@@ -2454,14 +2492,15 @@ static int mapres_finalize(const ntl_mapres *cR)
         lz.pending = false;
         if (e != hipSuccess) { lz.failed = fail(c, NTL_EDEVICE, std::string("map: ") + hipGetErrorString(e)); break; }
         if (R->reads && R->reads->gen != R->reads_gen && round == 0) {
+            /* unreachable for a grouped result: ntl_map_run_grouped completes both sketches (its two sketch_finalize calls) before it
+               queues anything, so reads->gen cannot move; its group tables were temporaries of that call and are gone */
+            if (R->grouped) { lz.failed = fail(c, NTL_EINTERNAL, "map: the read sketch of a grouped result was made again"); break; }
             memset(lz.slot, 0, sizeof(PinSlot));
-            const int rc = map_enqueue(c, (const ntl_index *)lz.holds[0].p, R->reads, R->d_rlen, R);
-            if (rc) { pending_abort(c, lz, rc, true); break; }
+            if (const int rc = map_enqueue(c, R)) { pending_abort(c, lz, rc, true); break; }
             continue;
         }
         const MapSums hs = *(const MapSums *)lz.slot;
-        R->n_maps = hs.tot[0]; R->n_hits = hs.tot[1]; R->n_pafs = hs.tot[2];
-        R->n_index_hits = hs.nfound;
+        R->n_maps = hs.tot[0]; R->n_hits = hs.tot[1]; R->n_pafs = hs.tot[2]; R->n_index_hits = hs.nfound;
         if (const char *m = map_check(*lz.slot, 0, R->hitf.get())) lz.failed = fail(c, NTL_EINTERNAL, m);
         break;
     }
@@ -2481,48 +2520,29 @@ extern "C" int ntl_map_run(ntl_ctx *c, const ntl_index *ix, const ntl_sketch *re
         HIPCHK(c, sync_both(reads->c));
     }
     const uint64_t nreads = reads->nseq;
-    ntl_mapres *R = new ntl_mapres();
-    R->c = c; R->params = *params; R->hitf = ix->hit_fraction;
-    ix->refs++;
-    R->lz.holds[0] = {ix, hold_index};
-    if (!R->lz.arm(c->pq)) { mapres_free(R); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
-    int rc = NTL_OK;
+    MapResPtr R = mapres_new(c, *params);
+    R->ix = ix; R->hitf = ix->hit_fraction;
+    ix->refs++; R->lz.holds[0] = {ix, hold_index};
+    if (!R->lz.arm(c->pq)) return mapres_fail(R, fail(c, NTL_EDEVICE, "out of events / page-locked slots"), false);
     /* read lengths: a sketch made from a batch that it still holds (pending) reads them from the batch (the `--len` column IS the
        sequence length); the result holds the batch too, until its kernels have run (mapres_finalize, or reap for a result destroyed
        before that).  Anything else -- or lengths that differ from the batch's -- is uploaded here. */
-    const uint32_t *d_rlen = nullptr;
     if (reads->src && reads->src->d_seq_len && nreads && memcmp(read_len, reads->src->seq_len.data(), nreads * 4) == 0) {
-        d_rlen = reads->src->d_seq_len;
-        const_cast<ntl_batch *>(reads->src)->refs++;
-        R->lz.holds[1] = {reads->src, hold_batch};
+        R->d_rlen = reads->src->d_seq_len;
+        const_cast<ntl_batch *>(reads->src)->refs++; R->lz.holds[1] = {reads->src, hold_batch};
+    } else {
+        if (int rc = R->rlen_own.alloc(c, (nreads + 1) * 4)) return mapres_fail(R, rc, false);
+        if (mapres_upload_lengths(R.get(), read_len, nreads, true)) return mapres_fail(R, fail(c, NTL_EDEVICE, "upload of the read lengths failed"), true);
     }
-    if (!d_rlen) {
-        if ((rc = R->rlen_own.alloc(c, (nreads + 1) * 4))) { mapres_free(R); return rc; }
-        if (nreads) {
-            const hipError_t e = hipMemcpyAsync(R->rlen_own.p, read_len, nreads * 4, hipMemcpyHostToDevice, c->stream);
-            if (e != hipSuccess || hipStreamSynchronize(c->stream) != hipSuccess) { /* pageable source: the caller's array is free again */
-                mapres_free(R);
-                return fail(c, NTL_EDEVICE, "upload of the read lengths failed");
-            }
-        }
-        d_rlen = R->rlen_own.as<uint32_t>();
-    }
-    R->d_rlen = d_rlen;
-    const_cast<ntl_sketch *>(reads)->refs++;
-    R->reads = reads;
-    if ((rc = map_enqueue(c, ix, reads, d_rlen, R))) {
-        pending_abort(c, R->lz, rc, true);
-        mapres_free(R);
-        return rc;
-    }
-    *out = R;
+    const_cast<ntl_sketch *>(reads)->refs++; R->reads = reads;
+    if (int rc = map_enqueue(c, R.get())) return mapres_fail(R, rc, true);
+    *out = R.release();
     return NTL_OK;
 }
 
 /* A completed result from the caller's records (the map side's ntl_sketch_from_host): no kernel, three uploads.  The hits keep the
    layout map_gather_kernel leaves -- regions that ascend with the mapping number, unused slots wherever the caller put them -- so that
-   densify and the text kernels see what they see behind the mapper.  Nothing is armed: lz stays as constructed (not pending, no
-   event, no slot, no holds), the result is neither grouped nor gap-shaped and has no map_off. */
+   densify and the text kernels see what they see behind the mapper.  Nothing is armed: everything but the records is as mapres_new made it. */
 extern "C" int ntl_mapres_from_host(ntl_ctx *c, const ntl_mapping *maps, uint64_t n_maps, const ntl_hit *hit_slots, uint64_t n_hit_slots,
                                     const ntl_paf *pafs, uint64_t n_pafs, ntl_mapres **out)
 {
@@ -2544,22 +2564,19 @@ extern "C" int ntl_mapres_from_host(ntl_ctx *c, const ntl_mapping *maps, uint64_
         at = M.hit_off + M.n_hits;
         n_hits += M.n_hits;
     }
-    static_assert(sizeof(ntl_mapping) == sizeof(MapRec) && sizeof(ntl_hit) == sizeof(HitRec) && sizeof(ntl_paf) == sizeof(PafRec),
-                  "ABI records must match the device records");
-    ntl_mapres *R = new ntl_mapres();
-    R->c = c; R->params = ntl_map_params();
+    MapResPtr R = mapres_new(c, ntl_map_params());
     R->n_maps = n_maps; R->n_hits = n_hits; R->n_pafs = n_pafs;
     R->rec_cap = std::max<uint64_t>(n_hit_slots, 1);
     int rc;
     if ((rc = R->maps.alloc(c, (n_maps + 1) * sizeof(MapRec))) || (rc = R->hits.alloc(c, (n_hit_slots + 1) * sizeof(HitRec))) ||
-        (rc = R->pafs.alloc(c, (n_pafs + 1) * sizeof(PafRec)))) { mapres_free(R); return rc; }
+        (rc = R->pafs.alloc(c, (n_pafs + 1) * sizeof(PafRec)))) return mapres_fail(R, rc, false);
     hipError_t e = hipSuccess;
     if (n_maps) e = hipMemcpyAsync(R->maps.p, maps, n_maps * sizeof(MapRec), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && n_hit_slots) e = hipMemcpyAsync(R->hits.p, hit_slots, n_hit_slots * sizeof(HitRec), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && n_pafs) e = hipMemcpyAsync(R->pafs.p, pafs, n_pafs * sizeof(PafRec), hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream); /* pageable sources: the caller's arrays are free again */
-    if (e != hipSuccess) { mapres_free(R); return fail(c, NTL_EDEVICE, hipGetErrorString(e)); }
-    *out = R;
+    if (e != hipSuccess) return mapres_fail(R, fail(c, NTL_EDEVICE, hipGetErrorString(e)), true); /* (nothing armed: no slot to scrub) */
+    *out = R.release();
     return NTL_OK;
 }
 
@@ -2606,66 +2623,46 @@ extern "C" int ntl_map_run_grouped(ntl_ctx *c, const ntl_sketch *ctg, const uint
     /* a large group's table has fewer than 4 n + 4 slots (at least 1024): all regions together must fit the 32-bit scan */
     if (4ull * ctg->count + 1024ull * n_groups >= 0xFFFFFFF0ull) return fail(c, NTL_EINVAL, "too many contig minimizers for one grouped call");
     const uint64_t n_ctg = ctg->nseq, nreads = reads->nseq;
-    ntl_mapres *R = new ntl_mapres();
-    R->c = c; R->params = *params; R->grouped = true;
+    MapResPtr R = mapres_new(c, *params);
+    R->grouped = true;
     R->gap_shaped = ctg->nseq == 2ull * n_groups && reads->nseq == n_groups;
     for (uint32_t g = 0; R->gap_shaped && g <= n_groups; g++) R->gap_shaped = ctg_group_off[g] == 2u * g && read_group_off[g] == g;
-    if (!R->lz.arm(c->pq)) { mapres_free(R); return fail(c, NTL_EDEVICE, "out of events / page-locked slots"); }
-    const_cast<ntl_sketch *>(ctg)->refs++;
-    R->lz.holds[0] = {ctg, hold_sketch};
-    const_cast<ntl_sketch *>(reads)->refs++;
-    R->reads = reads;
+    if (!R->lz.arm(c->pq)) return mapres_fail(R, fail(c, NTL_EDEVICE, "out of events / page-locked slots"), false);
+    const_cast<ntl_sketch *>(ctg)->refs++; R->lz.holds[0] = {ctg, hold_sketch};
+    const_cast<ntl_sketch *>(reads)->refs++; R->reads = reads;
     int rc = NTL_OK;
     DevBuf cg, rg, big, boff, next, scratch;
     const uint64_t ng1 = (uint64_t)n_groups + 1;
     if ((rc = R->ctg_len_own.alloc(c, (n_ctg + 1) * 4)) || (rc = R->rlen_own.alloc(c, (nreads + 1) * 4)) || (rc = cg.alloc(c, ng1 * 4)) ||
-        (rc = rg.alloc(c, ng1 * 4)) || (rc = big.alloc(c, 2 * ng1 * 4)) || (rc = boff.alloc(c, 2 * ng1 * 4)) || (rc = next.alloc(c, 4))) {
-        pending_abort(c, R->lz, rc);
-        mapres_free(R);
-        return rc;
-    }
-    auto bail = [&](int code, const std::string &m) {
-        pending_abort(c, R->lz, code, true);
-        mapres_free(R);
-        return fail(c, code, m);
-    };
-    {
-        hipError_t e = hipSuccess;
-        if (n_ctg) e = hipMemcpyAsync(R->ctg_len_own.p, ctg_len, n_ctg * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess && nreads) e = hipMemcpyAsync(R->rlen_own.p, read_len, nreads * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(cg.p, ctg_group_off, ng1 * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(rg.p, read_group_off, ng1 * 4, hipMemcpyHostToDevice, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(next.p, 0, 4, c->stream);
-        if (e == hipSuccess) e = hipMemsetAsync(big.p, 0, 2 * ng1 * 4, c->stream);
-        if (e != hipSuccess) return bail(NTL_EDEVICE, "upload of the lengths and group offsets failed");
-    }
-    R->d_rlen = R->rlen_own.as<uint32_t>();
-    GroupJob J;
-    memset(&J, 0, sizeof J);
+        (rc = rg.alloc(c, ng1 * 4)) || (rc = big.alloc(c, 2 * ng1 * 4)) || (rc = boff.alloc(c, 2 * ng1 * 4)) || (rc = next.alloc(c, 4)))
+        return mapres_fail(R, rc, false);
+    hipError_t e = mapres_upload_lengths(R.get(), read_len, nreads, false, ctg_len, n_ctg); /* (the scan below waits on MAIN); queued from here on */
+    if (e == hipSuccess) e = hipMemcpyAsync(cg.p, ctg_group_off, ng1 * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(rg.p, read_group_off, ng1 * 4, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(next.p, 0, 4, c->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(big.p, 0, 2 * ng1 * 4, c->stream);
+    if (e != hipSuccess) return mapres_fail(R, fail(c, NTL_EDEVICE, "upload of the lengths and group offsets failed"), true);
+    GroupJob J = {};
     J.A.cmx = ctg->records.as<MxRecord>(); J.A.c_off = ctg->mx_off.as<uint32_t>();
     J.A.rmx = reads->records.as<MxRecord>(); J.A.r_off = reads->mx_off.as<uint32_t>();
     J.A.cg_off = cg.as<uint32_t>(); J.A.rg_off = rg.as<uint32_t>(); J.A.n_groups = n_groups;
     J.A.big_off = boff.as<uint32_t>(); J.A.next = next.as<uint32_t>();
-    J.d_ctg_len = R->ctg_len_own.as<uint32_t>();
     /* regions of the large groups: one scan over their slot counts and one over a 1 per large group; the two totals are the call's
        one size that comes back (behind it the caller's arrays are free again, too) */
     uint32_t totals[2] = {0, 0};
     if (n_groups) {
         hipLaunchKernelGGL(group_size_kernel, dim3((n_groups + 255) / 256), dim3(256), 0, c->stream, J.A, big.as<uint32_t>());
-        if (hipGetLastError() != hipSuccess) return bail(NTL_EDEVICE, "group_size_kernel could not be launched");
-    }
-    if (n_groups) {
-        if ((rc = device_scan(c, big.as<uint32_t>(), boff.as<uint32_t>(), n_groups, totals, 2))) return bail(rc, c->err);
-    } else if (hipStreamSynchronize(c->stream) != hipSuccess) return bail(NTL_EDEVICE, "upload of the lengths and group offsets failed");
-    R->ginfo.lds_slots = GROUP_LDS_SLOTS;
-    R->ginfo.groups_in_global = totals[1];
-    R->ginfo.groups_in_lds = (uint64_t)n_groups - totals[1];
-    if ((rc = scratch.alloc(c, ((uint64_t)totals[0] + 1) * sizeof(IndexSlot)))) return bail(rc, c->err);
+        if (hipGetLastError() != hipSuccess) return mapres_fail(R, fail(c, NTL_EDEVICE, "group_size_kernel could not be launched"), true);
+        if ((rc = device_scan(c, big.as<uint32_t>(), boff.as<uint32_t>(), n_groups, totals, 2))) return mapres_fail(R, rc, true);
+    } else if (hipStreamSynchronize(c->stream) != hipSuccess)
+        return mapres_fail(R, fail(c, NTL_EDEVICE, "upload of the lengths and group offsets failed"), true);
+    R->ginfo.lds_slots = GROUP_LDS_SLOTS; R->ginfo.groups_in_global = totals[1]; R->ginfo.groups_in_lds = (uint64_t)n_groups - totals[1];
+    if ((rc = scratch.alloc(c, ((uint64_t)totals[0] + 1) * sizeof(IndexSlot)))) return mapres_fail(R, rc, true);
     J.A.scratch = scratch.as<IndexSlot>();
     static const int per_cu = occupancy_blocks(group_probe_kernel, GROUP_NT);
     J.grid = (unsigned)std::max<uint64_t>(1, std::min<uint64_t>(n_groups, (uint64_t)per_cu * (uint64_t)std::max(1, c->n_cu)));
-    if ((rc = map_enqueue(c, nullptr, reads, R->d_rlen, R, &J))) return bail(rc, c->err);
-    *out = R;
+    if ((rc = map_enqueue(c, R.get(), &J))) return mapres_fail(R, rc, true);
+    *out = R.release();
     return NTL_OK;
 }
 
@@ -2721,7 +2718,6 @@ struct ntl_gap_cands { std::vector<GapCand> rec; };
 static_assert(sizeof(ntl_gap_cand) == sizeof(GapCand) && sizeof(GapCand) == 32, "ABI record must match the device record");
 static_assert(NTL_GAPSEL_VALID == GSEL_VALID && NTL_GAPSEL_NEGATIVE == GSEL_NEGATIVE && NTL_GAPSEL_VIA_REVCOMP == GSEL_VIA_REVCOMP,
               "flag bits of the ABI and of gap_select_kernels.h");
-static_assert(sizeof(ntl_mapping) == sizeof(MapRec) && sizeof(ntl_hit) == sizeof(HitRec), "the reader's records are the device's");
 
 extern "C" int ntl_gap_pair_table(const uint64_t *keys, uint64_t n_pairs, uint64_t *slot_keys, uint32_t *slot_vals, uint64_t n_slots)
 {
@@ -2860,8 +2856,6 @@ extern "C" int ntl_mapres_download(const ntl_mapres *r, ntl_mapping *maps, ntl_h
     ntl_ctx *c = r->c;
     (void)hipSetDevice(c->device);
     if (int frc = mapres_finalize(r)) return frc;
-    static_assert(sizeof(ntl_mapping) == sizeof(MapRec) && sizeof(ntl_hit) == sizeof(HitRec) && sizeof(ntl_paf) == sizeof(PafRec),
-                  "ABI records must match the device records");
     if ((maps || hits) && r->n_maps) {
         if (int drc = mapres_densify(r)) return drc;
         if (maps) HIPCHK(c, hipMemcpyAsync(maps, r->maps_dense.p, r->n_maps * sizeof(MapRec), hipMemcpyDeviceToHost, c->stream));

@@ -177,6 +177,40 @@ def _destroyed_early(dev):
     ix.close(); csk.close()
 
 
+@pytest.mark.parametrize("make", DEVICES)
+def test_refused_map_calls_give_everything_back(make, monkeypatch):
+    """A map call that is refused after its result was armed (a sketch without records against another index than its own) hands
+    back slot, event and references through the one error exit: six refusals on a context with four slots, then ordinary work on
+    the same slots with the counts of its own outputs."""
+    monkeypatch.setenv("NTL_NSLOTS", "4")
+    dev = make(monkeypatch)
+    try:
+        _refused_then_mapped(dev)
+    finally:
+        dev.close()
+
+
+def _refused_then_mapped(dev):
+    contigs = pc.fixture_seqs("scaffolds_4.fa")
+    csk, ix, oix, ctg_len = _index(dev, contigs)
+    csk_b, ix_b, _, _ = _index(dev, contigs)
+    g = _reads()[0]
+    rl = np.array([len(s) for s in g], np.uint32)
+    with dev.batch(g) as rb, dev.sketch(rb, K, W, index=ix, records=False) as rsk:
+        for _ in range(6):
+            with pytest.raises(capi.NtlError, match="maps against the index it was made for only") as e:
+                dev.map(ix_b, rsk, rl, k=K, z=1000)
+            assert e.value.code == capi.NTL_EINVAL
+    ix_b.close(); csk_b.close()
+    for g in _reads():
+        qoff, qh, exp = _expected(oix, ctg_len, g)
+        rl = np.array([len(s) for s in g], np.uint32)
+        with dev.batch(g) as rb, dev.sketch(rb, K, W, index=ix, records=False) as rsk, dev.map(ix, rsk, rl, k=K, z=1000) as res:
+            _check_result(res, exp, _index_hits(oix, qh))
+    dev.sync()
+    ix.close(); csk.close()
+
+
 def _function_body(src, name):
     m = re.search(r"^(?:static |extern \"C\" )[^\n]*\b" + re.escape(name) + r"\(", src, re.M)
     assert m, name
@@ -194,6 +228,8 @@ def _function_body(src, name):
 
 # the stages sketch_enqueue is split into (mask_take, device_scan and launch_window_pass were separate before and stay out)
 SKETCH_STAGES = ["sketch_prepare", "g8k_for", "sketch_window_stage", "emit_grid", "emit_launch", "sketch_emit_stage"]
+# the stages map_enqueue is split into (device_scan was separate before and stays out)
+MAP_STAGES = ["map_prepare", "map_lookup_stage", "map_kernels_stage", "map_gather_stage"]
 
 
 def test_hot_path_queues_no_copies_or_fills():
@@ -202,7 +238,10 @@ def test_hot_path_queues_no_copies_or_fills():
     path (its totals) and to a batch without sequences."""
     src = open(os.path.join(ROOT, "ntlink_amd", "csrc", "ntl_hip.hip")).read()
     ops = re.compile(r"hip(?:Memcpy|Memset)(?:Async|D2D|D2H|H2D)?\s*\(")
-    assert not ops.findall(_function_body(src, "map_enqueue"))
+    map_top = _function_body(src, "map_enqueue")
+    for name in MAP_STAGES:  # map_enqueue itself calls every stage,
+        assert re.search(r"\b" + name + r"\(", map_top), name
+    assert not ops.findall(map_top + "".join(_function_body(src, name) for name in MAP_STAGES))  # and none of it copies or fills
     top = _function_body(src, "sketch_enqueue")
     stages = {name: _function_body(src, name) for name in SKETCH_STAGES}  # (asserts that each is found)
     body = top + "".join(stages.values())
