@@ -14,6 +14,8 @@
  *                                                      (bin/ntlink_patch_gaps.py:417-441)
  *   ntl_overlap_filter  valid-region + per-sequence   <- read_minimizer_line (bin/ntlink_overlap_sequences.py:170-190)
  *                 duplicate filter of the k15 w5 sketch
+ *   ntl_overlap_cuts  shared minimizers, their runs   <- merge_overlapping (bin/ntlink_overlap_sequences.py:341-417) with
+ *                 and the cut of every adjacent pair     filter_minimizers_position (:304-322), get_dist_from_end (:335-339)
  *   ntl_index_*   contig minimizer index            <- NtLink.read_minimizers
  *                                                      (bin/ntlink_pair.py:189-211)
  *   ntl_map_*     per-read lookup, hit filtering,   <- NtLink.find_scaffold_pairs body
@@ -314,6 +316,39 @@ int ntl_sketch_from_host(ntl_ctx *ctx, uint64_t nseq, const uint64_t *mx_off, co
  * the arrays); the input sketch is left alone. */
 int ntl_overlap_filter(ntl_ctx *ctx, const ntl_sketch *s, const uint64_t *region_off, const uint32_t *region_start,
                        const uint32_t *region_end, ntl_sketch **out);
+
+/* The cut points of adjacent contigs that overlap: merge_overlapping (bin/ntlink_overlap_sequences.py:341-417) for every pair of a
+ * path file in one device pass, on a sketch as ntl_overlap_filter returns it (per sequence the kept minimizers: unique hashes, in
+ * position order).  Nothing is changed but `out`; the call waits.
+ *
+ * ntl_overlap_pair, one per `source gap target` triple that qualifies (:461-468):
+ *   src, tgt              the two contigs' sequence numbers in the sketch
+ *   *_start, *_end        the pair's valid region on each, both ends inclusive (is_valid_pos :297-301): find_valid_mx_region
+ *                         (bin/ntlink_utils.py:189-197) of the source with source=True and of the target with source=False, a
+ *                         negative start clamped to 0
+ *   src_len, tgt_len      scaffolds[..].length, for get_dist_from_end (:335-339)
+ *   signs                 NTL_OVERLAP_SRC_MINUS / NTL_OVERLAP_TGT_MINUS where the node's sign in the path is '-'
+ * ntl_overlap_cut, one per pair:
+ *   status                NTL_OVERLAP_CUT: a cut was found (merge_overlapping returns True); NTL_OVERLAP_GLOBAL (diagnostics): the
+ *                         target slice held more than NTL_OVERLAP_LDS_SLICE minimizers and the pair took the global-scratch path
+ *   n_shared              minimizers in both slices (filter_minimizers_position, then ntjoin_utils.filter_minimizers)
+ *   n_comp                components of the weight-2 graph (build_graph :246-278, filter_graph_global :288-294): runs of consecutive
+ *                         shared minimizers in source order whose target ranks step by one
+ *   src_cut, tgt_cut      the chosen mid_mx's position on either contig (:409), for set_scaffold_info; 0 without a cut
+ *   hash                  that minimizer (path.mid_mx); 0 without a cut
+ * The best component is the maximum of (mapped_region_length, median_length_from_end, mid_mx) with mid_mx compared as the decimal
+ * string it is in the reference (:407-408); a component of two or more is walked from the end whose hash is the smaller string
+ * (:367-369).  The medians of two integers are compared as sums, in integers.
+ * NTL_EINVAL with a message: a sequence number outside the sketch, a region whose start lies behind its end, a NULL array with a
+ * non-zero count, a sketch without records, 2^31 pairs or more.  NTL_EINTERNAL: a slice that breaks the sketch's contract. */
+#define NTL_OVERLAP_CUT 1u
+#define NTL_OVERLAP_GLOBAL 2u
+#define NTL_OVERLAP_LDS_SLICE 1024u
+#define NTL_OVERLAP_SRC_MINUS 1u
+#define NTL_OVERLAP_TGT_MINUS 2u
+typedef struct { uint32_t src, tgt, src_start, src_end, tgt_start, tgt_end, src_len, tgt_len, signs, pad; } ntl_overlap_pair;
+typedef struct { uint32_t status, n_shared, n_comp, src_cut, tgt_cut, pad; uint64_t hash; } ntl_overlap_cut;
+int ntl_overlap_cuts(ntl_ctx *ctx, const ntl_sketch *s, const ntl_overlap_pair *pairs, uint64_t n_pairs, ntl_overlap_cut *out);
 
 /* ---- contig index ---------------------------------------------------------------------- */
 

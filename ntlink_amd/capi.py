@@ -24,7 +24,7 @@ SYMBOLS = [
     "ntl_ascii_create", "ntl_ascii_destroy", "ntl_ascii_nrec", "ntl_ascii_bytes", "ntl_stitch", "ntl_stitched_bytes", "ntl_stitched_copy", "ntl_stitched_destroy",
     "ntl_sketch_run", "ntl_sketch_run_indexed", "ntl_sketch_run_for_map", "ntl_sketch_has_records", "ntl_sketch_destroy", "ntl_sketch_nseq", "ntl_sketch_count", "ntl_sketch_download",
     "ntl_sketch_strips", "ntl_sketch_redo_strips", "ntl_sketch_fallback_strips", "ntl_sketch_from_lists", "ntl_sketch_plan", "ntl_sketch_wait", "ntl_mapres_wait",
-    "ntl_sketch_from_host", "ntl_overlap_filter",
+    "ntl_sketch_from_host", "ntl_overlap_filter", "ntl_overlap_cuts",
     "ntl_index_build", "ntl_index_destroy", "ntl_index_size",
     "ntl_map_run", "ntl_mapres_destroy", "ntl_mapres_n_mappings", "ntl_mapres_n_hits", "ntl_mapres_n_pafs",
     "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_mapres_from_host", "ntl_map_run_grouped", "ntl_mapres_grouped_info", "ntl_mapres_gap_cuts",
@@ -52,6 +52,10 @@ GAP_CAND_DT = np.dtype([(nm, "<u4") for nm in ("pair", "read", "anchors", "flags
 NTL_GAPSEL_VALID, NTL_GAPSEL_NEGATIVE, NTL_GAPSEL_VIA_REVCOMP = 1, 2, 4
 STITCH_SEG_DT = np.dtype([(nm, "<u4") for nm in ("store", "rec", "lo", "hi", "flags")])  # ntl_stitch_seg
 NTL_STITCH_FILL, NTL_STITCH_REVCOMP, NTL_STITCH_LOWER, NTL_STITCH_LOWER_FIRST = 0xFFFFFFFF, 1, 2, 4
+OVERLAP_PAIR_DT = np.dtype([(nm, "<u4") for nm in ("src", "tgt", "src_start", "src_end", "tgt_start", "tgt_end", "src_len", "tgt_len", "signs",
+                                                   "pad")])  # ntl_overlap_pair
+OVERLAP_CUT_DT = np.dtype([(nm, "<u4") for nm in ("status", "n_shared", "n_comp", "src_cut", "tgt_cut", "pad")] + [("hash", "<u8")])  # ntl_overlap_cut
+NTL_OVERLAP_CUT, NTL_OVERLAP_GLOBAL, NTL_OVERLAP_LDS_SLICE, NTL_OVERLAP_SRC_MINUS, NTL_OVERLAP_TGT_MINUS = 1, 2, 1024, 1, 2
 NO_CTG = 0xFFFFFFFF  # ntl_mapping.ctg of a name that is not in the reader's table
 
 
@@ -161,6 +165,7 @@ def load(path=None):
     L.ntl_sketch_download.argtypes = [vp, u64p, u64p, u32p, u8p]
     L.ntl_sketch_from_host.argtypes = [vp, C.c_uint64, u64p, u64p, u32p, u8p, C.POINTER(vp)]
     L.ntl_overlap_filter.argtypes = [vp, vp, u64p, u32p, u32p, C.POINTER(vp)]
+    L.ntl_overlap_cuts.argtypes = [vp, vp, vp, C.c_uint64, vp]
     L.ntl_index_build.argtypes = [vp, vp, u32p, C.c_uint32, C.POINTER(vp)]
     L.ntl_index_destroy.argtypes = [vp]
     L.ntl_index_destroy.restype = None
@@ -767,6 +772,18 @@ class Device:
         self._chk(self.L.ntl_overlap_filter(self.ptr, sketch.ptr, _ptr(ro, C.c_uint64), _ptr(rs, C.c_uint32), _ptr(re, C.c_uint32),
                                             C.byref(p)))
         return Sketch(self, p)
+
+    def overlap_cuts(self, sketch, pairs):
+        """The cut points of adjacent overlapping contigs (ntl_overlap_cuts, csrc/overlap_cut_kernels.h): `sketch` as overlap_filter
+        returns it, `pairs` OVERLAP_PAIR_DT records (or tuples) -- the two sequence numbers, each side's inclusive valid region, the
+        two lengths, the signs.  -> OVERLAP_CUT_DT records, one per pair: status (NTL_OVERLAP_CUT: a cut was found), the numbers of
+        shared minimizers and of components, the two cuts and the chosen minimizer.  Waits for the device."""
+        pr = np.ascontiguousarray(pairs if isinstance(pairs, np.ndarray) else np.array(list(pairs), OVERLAP_PAIR_DT), OVERLAP_PAIR_DT)
+        if pr.ndim != 1:
+            raise ValueError("pairs must be one-dimensional")
+        out = np.zeros(len(pr), OVERLAP_CUT_DT)
+        self._chk(self.L.ntl_overlap_cuts(self.ptr, sketch.ptr, pr.ctypes.data if len(pr) else None, len(pr), out.ctypes.data if len(pr) else None))
+        return out
 
     def gap_select(self, block, ctg_len, large_k, table):
         """The candidates of one block of verbose mappings (ntl_gap_select, csrc/gap_select_kernels.h): `block` as formats.read_verbose

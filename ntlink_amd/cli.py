@@ -4,6 +4,7 @@
   ntlink_pair_main  `ntlink_pair.py ...` with the reference's argparse               (bin/ntlink_pair.py:509-536)
   ntlink_main       `ntLink pair target= reads= [k= w= ...]` make-style key=value    (ntLink:8-89,165)
   patch_gaps_main   `ntlink_patch_gaps.py ...` with the reference's argparse         (bin/ntlink_patch_gaps.py:760-784)
+  overlap_sequences_main  `ntlink_overlap_sequences.py ...`, `-m` optional           (bin/ntlink_overlap_sequences.py:552-568)
 """
 import argparse
 import os
@@ -121,6 +122,52 @@ def patch_gaps_main(argv=None):
         gapfill.patch_gaps(a, dev)
     finally:
         dev.close()
+    return 0
+
+
+def overlap_sequences_parser():
+    p = argparse.ArgumentParser(description="Find coordinates for combining overlapping sequences")
+    p.add_argument("-m", help="Minimizer TSV file, - for standard input; without it the contigs that may overlap are sketched here, "
+                              "at (k, 5), and no minimizer text is read", type=str, default=None)
+    p.add_argument("-f", help="Fudge factor for estimated overlap [0.5]", type=float, default=0.5)
+    p.add_argument("-a", "--path", help="Path file", required=True, type=str)
+    p.add_argument("-s", "--fasta", help="Scaffold sequences", required=True, type=str)
+    p.add_argument("-k", help="Indexlr k", required=True, type=int)
+    p.add_argument("-d", help="Scaffold dot file", required=True, type=str)
+    p.add_argument("-g", help="Minimum gap size (bp) [20]", default=20, type=int)
+    p.add_argument("--outgap", help="Gap size between trimmed overlapping sequences (bp) [2]", default=2, type=int)
+    p.add_argument("-p", help="Output file prefix [ntlink_merge]", default="ntlink_merge", type=str)
+    p.add_argument("-v", help="Verbose output logging: refused, the .mx.dot graph it asks for is never built here", action="store_true")
+    p.add_argument("--trim_info", help="Verbose log of trimming info", action="store_true")
+    p.add_argument("--version", action="version", version="ntLink v1.3.11")
+    p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    return p
+
+
+def overlap_sequences_main(argv=None):
+    """The overlap stage (overlap.overlap_sequences): the reference's arguments, parameter block and log lines
+    (bin/ntlink_overlap_sequences.py:552-608).  Any error: a message, no output file left, exit status 1."""
+    import datetime
+    a = overlap_sequences_parser().parse_args(argv)
+    print("Assessing putative overlaps...")
+    print("Parameters for overlap stage:")
+    for flag, value in (("-m", a.m), ("-f", a.f), ("-a", a.path), ("-s", a.fasta), ("-k", a.k), ("-d", a.d), ("-g", a.g), ("--outgap", a.outgap),
+                        ("-p", a.p)):
+        print(f"\t{flag}", value)
+    if a.v:
+        print("ERROR: -v is not available: it prints the minimizer graph of every pair, and no graph is built here", file=sys.stderr)
+        return 1
+    from . import overlap
+    try:
+        dev = _device(a.device)
+        try:
+            overlap.overlap_sequences(a, dev)
+        finally:
+            dev.close()
+    except Exception as exc:
+        print(f"ERROR: {type(exc).__name__}: {exc}", file=sys.stderr)
+        return 1
+    print(datetime.datetime.today(), ": DONE!", flush=True)
     return 0
 
 

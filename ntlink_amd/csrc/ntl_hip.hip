@@ -39,6 +39,7 @@
 #include "mask_kernels.h"
 #include "stitch_kernels.h"
 #include "overlap_kernels.h"
+#include "overlap_cut_kernels.h"
 #include "format_kernels.h"
 
 #define NTL_END_PAD 4096u /* bases of padding behind the last sequence (rolling over-reads) */
@@ -2196,6 +2197,67 @@ extern "C" int ntl_overlap_filter(ntl_ctx *c, const ntl_sketch *s, const uint64_
     }
     HIPCHK(c, hipStreamSynchronize(c->stream)); /* roff32 and the caller's region arrays are free again */
     *out = o.release();
+    return NTL_OK;
+}
+
+static_assert(sizeof(ntl_overlap_pair) == sizeof(OvcPair) && sizeof(OvcPair) == 40 && sizeof(ntl_overlap_cut) == sizeof(OvcCut) && sizeof(OvcCut) == 32,
+              "ABI records must match the device records");
+static_assert(NTL_OVERLAP_CUT == OVC_CUT && NTL_OVERLAP_GLOBAL == OVC_GLOBAL && NTL_OVERLAP_LDS_SLICE == OVC_LDS_SLICE &&
+              NTL_OVERLAP_SRC_MINUS == OVC_SRC_MINUS && NTL_OVERLAP_TGT_MINUS == OVC_TGT_MINUS, "constants of the ABI and of overlap_cut_kernels.h");
+
+/* merge_overlapping of bin/ntlink_overlap_sequences.py:341-417 for every pair at once (overlap_cut_kernels.h).  One wait when every
+   target slice fits the LDS table; a second one behind the overflow kernel, whose scratch is sized by the first. */
+extern "C" int ntl_overlap_cuts(ntl_ctx *c, const ntl_sketch *s, const ntl_overlap_pair *pairs, uint64_t n_pairs, ntl_overlap_cut *out)
+{
+    if (!c || !s || (n_pairs && (!pairs || !out))) return NTL_EINVAL;
+    (void)hipSetDevice(c->device);
+    if (s->c->device != c->device) return fail(c, NTL_EINVAL, "ntl_overlap_cuts: the sketch lives on another device");
+    if (s->no_records) return fail(c, NTL_EINVAL, "a sketch made by ntl_sketch_run_for_map holds no records");
+    if (int frc = sketch_finalize(s)) return frc;
+    if (n_pairs >= ((uint64_t)1 << 31)) return fail(c, NTL_EINVAL, "ntl_overlap_cuts: too many pairs for one call");
+    for (uint64_t i = 0; i < n_pairs; i++) {
+        const ntl_overlap_pair &P = pairs[i];
+        if (P.src >= s->nseq || P.tgt >= s->nseq)
+            return fail(c, NTL_EINVAL, "ntl_overlap_cuts: pair " + std::to_string(i) + " names a sequence the sketch does not hold");
+        if (P.src_start > P.src_end || P.tgt_start > P.tgt_end)
+            return fail(c, NTL_EINVAL, "ntl_overlap_cuts: pair " + std::to_string(i) + " has a region that starts behind its end");
+    }
+    if (!n_pairs) return NTL_OK;
+    DevBuf dpairs, dout, list, info, scratch;
+    int rc;
+    if ((rc = dpairs.alloc(c, n_pairs * sizeof(OvcPair))) || (rc = dout.alloc(c, n_pairs * sizeof(OvcCut))) || (rc = list.alloc(c, n_pairs * 4)) ||
+        (rc = info.alloc(c, 16)))
+        return rc;
+    OvcArgs A = {};
+    A.rec = s->records.as<MxRecord>(); A.mx_off = s->mx_off.as<uint32_t>(); A.pairs = dpairs.as<OvcPair>(); A.n_pairs = (uint32_t)n_pairs;
+    A.out = dout.as<OvcCut>(); A.over_list = list.as<uint32_t>(); A.info = info.as<uint32_t>();
+    uint32_t hinfo[4] = {0, 0, 0, 0};
+    {
+        ProfSpan sp(c, "overlap_cut");
+        HIPCHK(c, hipMemcpyAsync(dpairs.p, pairs, n_pairs * sizeof(OvcPair), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(info.p, 0, 16, c->stream));
+        hipLaunchKernelGGL(overlap_cut_kernel, dim3((unsigned)n_pairs), dim3(OVC_NT), 0, c->stream, A);
+        HIPCHK(c, hipGetLastError());
+    }
+    HIPCHK(c, hipMemcpyAsync(hinfo, info.p, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, dout.p, n_pairs * sizeof(OvcCut), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, main_wait(c));
+    if (hinfo[0]) { /* target slices above OVC_LDS_SLICE: the same body over global scratch, sized now that the longest is known */
+        const unsigned blocks = std::min<uint32_t>(hinfo[0], OVC_OVER_BLOCKS);
+        A.slab_cap = hinfo[1];
+        A.slab_bytes = ((uint64_t)OVC_SLAB_BYTES_PER_MX * hinfo[1] + 255) & ~(uint64_t)255;
+        if ((rc = scratch.alloc(c, A.slab_bytes * blocks))) return rc;
+        A.scratch = scratch.as<uint8_t>();
+        {
+            ProfSpan sp(c, "overlap_cut_overflow");
+            hipLaunchKernelGGL(overlap_cut_overflow_kernel, dim3(blocks), dim3(OVC_NT), 0, c->stream, A);
+            HIPCHK(c, hipGetLastError());
+        }
+        HIPCHK(c, hipMemcpyAsync(hinfo, info.p, 16, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, dout.p, n_pairs * sizeof(OvcCut), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, main_wait(c));
+    }
+    if (hinfo[2]) return fail(c, NTL_EINTERNAL, "ntl_overlap_cuts: a pair's slices broke the sketch's contract (a hash twice in one sequence, or a probe sequence without an end)");
     return NTL_OK;
 }
 

@@ -919,18 +919,28 @@ def print_gap_filled_sequences(pairs, sequences, scaffolds, reads, args, dev=Non
     if scaffolds.ascii is None or reads.ascii is None:
         raise ValueError("the scaffolds' and the reads' bytes must be resident (stitchable=True)")
     plan = plan or output_plan(args.path, pairs, sequences, args)
+    write_stitched_records(dev, args.o, [scaffolds.ascii, reads.ascii], _record_segments(plan, sequences, scaffolds, reads), max_bytes)
+    print_filling_stats(plan.counters, file=stats_file)
+    return plan
+
+
+def write_stitched_records(dev, path, stores, records, max_bytes=STITCH_BYTES):
+    """Writes `path`: per record its header, its segments and a newline, assembled on the device (Device.stitch) from the resident
+    `stores` (capi.Ascii).  records: (header bytes, [(store, rec, lo, hi, flags)], bytes of text) each; the headers of a call are
+    one more store behind `stores`.  Whole records of at most max_bytes of text per call; the text comes back in pieces into
+    page-locked memory and goes to the file through ntl_write_blob.  The writer of the gap filler's and of the overlap stage's FASTA."""
     newline = (capi.NTL_STITCH_FILL, ord("\n"), 0, 1, 0)
-    fd = os.open(args.o, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+    fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
     buf = None
     try:
-        for call in _stitch_calls(_record_segments(plan, sequences, scaffolds, reads), max_bytes):
+        for call in _stitch_calls(records, max_bytes):
             segs = []
             for i, (header, rec_segs, _size) in enumerate(call):
-                segs.append((2, i, 0, len(header), 0))
+                segs.append((len(stores), i, 0, len(header), 0))
                 segs += rec_segs
                 segs.append(newline)
             with dev.ascii([header for header, _segs, _size in call]) as headers, \
-                    dev.stitch([scaffolds.ascii, reads.ascii, headers], np.array(segs, capi.STITCH_SEG_DT)) as text:
+                    dev.stitch(list(stores) + [headers], np.array(segs, capi.STITCH_SEG_DT)) as text:
                 total = text.nbytes
                 if buf is None or len(buf) < min(total, WRITE_PIECE):
                     dev.pinned_release(buf)
@@ -939,12 +949,10 @@ def print_gap_filled_sequences(pairs, sequences, scaffolds, reads, args, dev=Non
                     hi = min(total, lo + len(buf))
                     text.copy(lo, hi, buf)
                     if dev.L.ntl_write_blob(fd, buf.ctypes.data, hi - lo) != 0:
-                        raise OSError(f"{args.o}: write failed")
+                        raise OSError(f"{path}: write failed")
     finally:
         os.close(fd)
         dev.pinned_release(buf)
-    print_filling_stats(plan.counters, file=stats_file)
-    return plan
 
 
 def print_agp(pairs, sequences, args, plan=None):
