@@ -38,6 +38,8 @@
  *                                                      bin/ntlink_paf_output.py:131-135
  *   ntl_tally_*   contig-pair tally                 <- bin/ntlink_pair.py:416-435,315-334,157-239
  *   ntl_liftover  verbose mappings through an AGP   <- bin/ntlink_liftover_mappings.py:61-143 (ntLink_rounds:124-125)
+ *   ntl_mapres_liftover  the same on a resident     <- liftover_ctg_mappings, print_adjusted_mappings (:61-121)
+ *                 map result, on the device
  *
  * Conventions: every call returns 0 on success or a negative NTL_E* code; the message is
  * available from ntl_last_error().  All pointers in signatures are HOST pointers unless the
@@ -422,6 +424,35 @@ int ntl_mapres_download(const ntl_mapres *r, ntl_mapping *maps, ntl_hit *hits, n
 int ntl_mapres_from_host(ntl_ctx *ctx, const ntl_mapping *maps, uint64_t n_maps, const ntl_hit *hit_slots, uint64_t n_hit_slots,
                          const ntl_paf *pafs, uint64_t n_pafs, ntl_mapres **out);
 
+/* The liftover of a resident result through an AGP: liftover_ctg_mappings and print_adjusted_mappings of
+ * bin/ntlink_liftover_mappings.py:61-121 (ntLink_rounds:122-125) over records instead of lines (csrc/liftover_kernels.h; ntl_liftover
+ * below is the host form, file to file).  table[n_ctg] has one entry per contig number of the INPUT result's contig name space.
+ * Per mapping (one input line): mode 0 keeps the line for the grouping and drops its hits; otherwise a hit stays iff
+ * ctg_start - 1 <= ctg_pos <= ctg_end - k (signed: with k longer than the component none stays), and with adjust = ctg_pos -
+ * (ctg_start - 1), offset = scaf_start - 1 its position becomes offset + adjust (mode 2), offset + (ctg_end - ctg_start + 1 - adjust) - k
+ * with the contig strand flipped (mode 3), or stays (mode 1).
+ * Per read (consecutive mappings with equal .read): runs of consecutive lines with equal new_ctg; a name keeps the index of its FIRST
+ * run; a later run of a known name marks every name whose run lies strictly between the two as subsumed (by name: a name may mark
+ * itself, two names each other); the lines of subsumed names go, the remaining consecutive lines of one name are a group, whose kept
+ * hits are concatenated in order; a group that is not empty and whose contig positions strictly increase or strictly decrease (one
+ * hit does) is one output mapping: n_hits the concatenated count, ctg the new_ctg, read unchanged, input order.
+ * *out is an ordinary, completed, non-grouped result without PAF records and with n_index_hits = 0; its hits sit in per-mapping
+ * regions that ascend with the mapping number, as ntl_mapres_from_host documents.  `in` is completed by the call, left alone, and may be
+ * destroyed afterwards.  One host wait.  Event name for ntl_prof_get: "liftover".
+ * NTL_EINVAL with a message: a mapping whose ctg >= n_ctg (the reader's 0xFFFFFFFF among them), a mode above 3, an entry of mode 1 to
+ * 3 with scaf_start or ctg_start of 0 or ctg_end < ctg_start, k < 1.  NTL_ERANGE: a lifted position does not fit 32 bits (computed in 64
+ * bits on the device, reported at the wait).  No partial result in either case.
+ * NTL_LIFT_LANE_LINES: a read of at most so many lines is grouped by one lane, a longer one by a wavefront (the result is the same). */
+typedef struct {            /* one per contig number of the INPUT result's contig name space */
+    uint32_t new_ctg;       /* number in the OUTPUT name space (path id; the contig's own name where it is not in the AGP) */
+    uint32_t mode;          /* 0 = not in the AGP (line kept for grouping, every hit dropped)
+                               1 = in the AGP, positions left alone (path id == contig id, or orientation neither + nor -)
+                               2 = shift (+), 3 = mirror and flip the contig strand (-) */
+    uint32_t scaf_start, ctg_start, ctg_end;   /* 1-based inclusive, as in the AGP; ignored for mode 0 */
+} ntl_lift_entry;
+#define NTL_LIFT_LANE_LINES 16u
+int ntl_mapres_liftover(ntl_ctx *ctx, const ntl_mapres *in, const ntl_lift_entry *table, uint32_t n_ctg, int32_t k, ntl_mapres **out);
+
 /* Grouped mapping: ntl_index_build + ntl_map_run once per group, on that group's contigs and reads alone, in one device pass -- the
  * gap filler's re-mapping loop (map_long_reads, bin/ntlink_patch_gaps.py:412-442: per gap one read piece against the minimizer dict
  * of the two scaffold ends around it, read_btllib_minimizers :397-410).  Group g = the contigs [ctg_group_off[g], ctg_group_off[g+1])
@@ -660,7 +691,7 @@ int ntl_tally_write(const ntl_tally *t, int a, int min_n, const char *pairs_path
 /* errno of the calling thread's last call that returned NTL_EIO (0: none). */
 int ntl_io_errno(void);
 
-/* ---- liftover of the verbose mappings (no GPU involved) -------------------------------------- */
+/* ---- liftover of the verbose mappings, file to file (no GPU involved; ntl_mapres_liftover is the device form) ---- */
 
 /* <prefix>.verbose_mapping.tsv moved to the coordinates of the scaffolds an AGP describes, file to file: the work of
  * bin/ntlink_liftover_mappings.py (liftover_ctg_mappings :61-87, print_adjusted_mappings :89-121, liftover_mappings

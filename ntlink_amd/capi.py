@@ -27,7 +27,7 @@ SYMBOLS = [
     "ntl_sketch_from_host", "ntl_overlap_filter", "ntl_overlap_cuts",
     "ntl_index_build", "ntl_index_destroy", "ntl_index_size",
     "ntl_map_run", "ntl_mapres_destroy", "ntl_mapres_n_mappings", "ntl_mapres_n_hits", "ntl_mapres_n_pafs",
-    "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_mapres_from_host", "ntl_map_run_grouped", "ntl_mapres_grouped_info", "ntl_mapres_gap_cuts",
+    "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_mapres_from_host", "ntl_mapres_liftover", "ntl_map_run_grouped", "ntl_mapres_grouped_info", "ntl_mapres_gap_cuts",
     "ntl_fastx_open", "ntl_fastx_open_range", "ntl_fastx_range", "ntl_fastx_close", "ntl_fastx_error", "ntl_fastx_next", "ntl_fastx_sizes", "ntl_fastx_copy", "ntl_fastx_copy_packed", "ntl_fastx_runs", "ntl_fastx_next_span", "ntl_fastx_parse_span", "ntl_fastx_copy_span", "ntl_fastx_seqs", "ntl_fastx_offsets",
     "ntl_fastx_names", "ntl_fastx_name_offsets", "ntl_write_indexlr", "ntl_write_verbose", "ntl_write_paf",
     "ntl_tsv_open", "ntl_tsv_close", "ntl_tsv_error", "ntl_tsv_next", "ntl_tsv_sizes", "ntl_tsv_copy",
@@ -56,6 +56,9 @@ OVERLAP_PAIR_DT = np.dtype([(nm, "<u4") for nm in ("src", "tgt", "src_start", "s
                                                    "pad")])  # ntl_overlap_pair
 OVERLAP_CUT_DT = np.dtype([(nm, "<u4") for nm in ("status", "n_shared", "n_comp", "src_cut", "tgt_cut", "pad")] + [("hash", "<u8")])  # ntl_overlap_cut
 NTL_OVERLAP_CUT, NTL_OVERLAP_GLOBAL, NTL_OVERLAP_LDS_SLICE, NTL_OVERLAP_SRC_MINUS, NTL_OVERLAP_TGT_MINUS = 1, 2, 1024, 1, 2
+LIFT_ENTRY_DT = np.dtype([(nm, "<u4") for nm in ("new_ctg", "mode", "scaf_start", "ctg_start", "ctg_end")])  # ntl_lift_entry
+NTL_LIFT_ABSENT, NTL_LIFT_KEEP, NTL_LIFT_SHIFT, NTL_LIFT_MIRROR = 0, 1, 2, 3  # ntl_lift_entry.mode
+NTL_LIFT_LANE_LINES = 16
 NO_CTG = 0xFFFFFFFF  # ntl_mapping.ctg of a name that is not in the reader's table
 
 
@@ -183,6 +186,7 @@ def load(path=None):
         f.restype = C.c_uint64
     L.ntl_mapres_download.argtypes = [vp, vp, vp, vp]
     L.ntl_mapres_from_host.argtypes = [vp, vp, C.c_uint64, vp, C.c_uint64, vp, C.c_uint64, C.POINTER(vp)]
+    L.ntl_mapres_liftover.argtypes = [vp, vp, vp, C.c_uint32, C.c_int32, C.POINTER(vp)]
     L.ntl_host_alloc.argtypes = [vp, C.c_uint64, C.POINTER(vp)]
     L.ntl_host_free.argtypes = [vp, vp]
     L.ntl_host_free.restype = None
@@ -843,6 +847,17 @@ class Device:
         p = C.c_void_p()
         self._chk(self.L.ntl_mapres_from_host(self.ptr, m.ctypes.data if len(m) else None, len(m), h.ctypes.data if len(h) else None, len(h),
                                               q.ctypes.data if len(q) else None, len(q), C.byref(p)))
+        return MapResult(self, p)
+
+    def mapres_liftover(self, result, table, k):
+        """`result` lifted through an AGP on the device (ntl_mapres_liftover, csrc/liftover_kernels.h): table = LIFT_ENTRY_DT records (or
+        tuples), one per contig number of the result's contig name space -- liftover.lift_table makes it from an AGP.  -> a new,
+        completed MapResult in the output name space (no PAF records); `result` is completed, left alone and may be closed."""
+        tb = np.ascontiguousarray(table if isinstance(table, np.ndarray) else np.array(list(table), LIFT_ENTRY_DT), LIFT_ENTRY_DT)
+        if tb.ndim != 1:
+            raise ValueError("table must be one-dimensional")
+        p = C.c_void_p()
+        self._chk(self.L.ntl_mapres_liftover(self.ptr, result.ptr, tb.ctypes.data if len(tb) else None, len(tb), int(k), C.byref(p)))
         return MapResult(self, p)
 
     def map_grouped(self, contig_sketch, ctg_len, ctg_group_off, read_sketch, read_len, read_group_off, k, z=1000, x=0.0, sensitive=False,

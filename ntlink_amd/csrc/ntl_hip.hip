@@ -41,6 +41,7 @@
 #include "overlap_kernels.h"
 #include "overlap_cut_kernels.h"
 #include "format_kernels.h"
+#include "liftover_kernels.h"
 
 #define NTL_END_PAD 4096u /* bases of padding behind the last sequence (rolling over-reads) */
 #define SK_NT 256
@@ -2925,6 +2926,85 @@ extern "C" int ntl_mapres_download(const ntl_mapres *r, ntl_mapping *maps, ntl_h
     }
     if (pafs && r->n_pafs) HIPCHK(c, hipMemcpyAsync(pafs, r->pafs.p, r->n_pafs * sizeof(PafRec), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, main_wait(c));
+    return NTL_OK;
+}
+
+/* ------------------------------------------------------------------ liftover of a resident result ---- */
+
+static_assert(sizeof(ntl_lift_entry) == sizeof(LiftEntry) && sizeof(LiftEntry) == 20 && sizeof(LiftLine) == 16 && sizeof(LiftInfo) == 16,
+              "ABI record must match the device record");
+static_assert(NTL_LIFT_LANE_LINES == LIFT_LANE_LINES, "constant of the ABI and of liftover_kernels.h");
+
+/* Five launches and a scan on MAIN (liftover_kernels.h), all sized by the input's counts, and ONE wait behind them: the error word,
+   the hits and the mappings of the output come back together.  Every temporary is a block of the context's cache. */
+extern "C" int ntl_mapres_liftover(ntl_ctx *c, const ntl_mapres *in, const ntl_lift_entry *table, uint32_t n_ctg, int32_t k, ntl_mapres **out)
+{
+    if (!c || !in || !out) return NTL_EINVAL;
+    *out = nullptr;
+    (void)hipSetDevice(c->device);
+    if (n_ctg && !table) return fail(c, NTL_EINVAL, "ntl_mapres_liftover: a null table with a non-zero count");
+    if (k < 1) return fail(c, NTL_EINVAL, "ntl_mapres_liftover: k must be at least 1");
+    if (in->c->device != c->device) return fail(c, NTL_EINVAL, "ntl_mapres_liftover: the result lives on another device");
+    for (uint32_t i = 0; i < n_ctg; i++) {
+        const ntl_lift_entry &E = table[i];
+        if (E.mode > 3u) return fail(c, NTL_EINVAL, "ntl_mapres_liftover: table entry " + std::to_string(i) + " has mode " + std::to_string(E.mode));
+        if (E.mode && (!E.scaf_start || !E.ctg_start))
+            return fail(c, NTL_EINVAL, "ntl_mapres_liftover: table entry " + std::to_string(i) + " has a start of 0 (AGP coordinates count from 1)");
+        if (E.mode && E.ctg_end < E.ctg_start)
+            return fail(c, NTL_EINVAL, "ntl_mapres_liftover: table entry " + std::to_string(i) + " ends in front of its start");
+    }
+    if (int frc = mapres_finalize(in)) return fail(c, frc, "ntl_mapres_liftover: the input result failed: " + in->c->err);
+    if (in->c != c) HIPCHK(c, sync_both(in->c)); /* its records were made on another context's streams */
+    const uint64_t n_maps = in->n_maps, cap = in->rec_cap;
+    MapResPtr R = mapres_new(c, ntl_map_params());
+    R->rec_cap = std::max<uint64_t>(cap, 1);
+    int rc;
+    if ((rc = R->maps.alloc(c, (n_maps + 1) * sizeof(MapRec))) || (rc = R->hits.alloc(c, (cap + 1) * sizeof(HitRec))) ||
+        (rc = R->pafs.alloc(c, sizeof(PafRec)))) return mapres_fail(R, rc, false);
+    if (!n_maps) { *out = R.release(); return NTL_OK; }
+    DevBuf tab, kept, line, bytes, words, info;
+    if ((rc = tab.alloc(c, ((uint64_t)n_ctg + 1) * sizeof(LiftEntry))) || (rc = kept.alloc(c, (cap + 1) * sizeof(HitRec))) ||
+        (rc = line.alloc(c, n_maps * sizeof(LiftLine))) || (rc = bytes.alloc(c, 3 * n_maps)) || (rc = words.alloc(c, (5 * n_maps + 1) * 4)) ||
+        (rc = info.alloc(c, sizeof(LiftInfo))))
+        return mapres_fail(R, rc, false);
+    LiftArgs A = {};
+    A.maps = in->maps.as<MapRec>(); A.hits = in->hits.as<HitRec>(); A.hits_cap = cap;
+    A.n_maps = (uint32_t)n_maps; A.n_ctg = n_ctg; A.k = k; A.table = tab.as<LiftEntry>();
+    A.kept_hits = kept.as<HitRec>(); A.line = line.as<LiftLine>();
+    A.mono = bytes.as<uint8_t>(); A.cov = A.mono + n_maps; A.drop = A.cov + n_maps;
+    A.gfirst = words.as<uint32_t>(); A.goff = A.gfirst + n_maps; A.gcnt = A.goff + n_maps; A.over_list = A.gcnt + n_maps; A.emit = A.over_list + n_maps;
+    A.info = info.as<LiftInfo>();
+    A.out_maps = R->maps.as<MapRec>(); A.out_hits = R->hits.as<HitRec>();
+    LiftInfo hinfo = {};
+    uint32_t n_out = 0;
+    hipError_t e = hipSuccess;
+    {
+        ProfSpan sp(c, "liftover");
+        if (n_ctg) e = hipMemcpyAsync(tab.p, table, (uint64_t)n_ctg * sizeof(LiftEntry), hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(info.p, 0, sizeof(LiftInfo), c->stream);
+        if (e == hipSuccess) {
+            const unsigned per_wave = (unsigned)((n_maps + LIFT_NT / 64 - 1) / (LIFT_NT / 64)), per_lane = (unsigned)((n_maps + LIFT_NT - 1) / LIFT_NT);
+            hipLaunchKernelGGL(lift_line_kernel, dim3(per_wave), dim3(LIFT_NT), 0, c->stream, A);
+            hipLaunchKernelGGL(lift_read_kernel, dim3(per_lane), dim3(LIFT_NT), 0, c->stream, A);
+            hipLaunchKernelGGL(lift_read_overflow_kernel, dim3((unsigned)std::min<uint64_t>(n_maps / (LIFT_LANE_LINES + 1) + 1, LIFT_OVER_BLOCKS)), dim3(64), 0,
+                               c->stream, A);
+            e = hipGetLastError();
+            if (e == hipSuccess && (rc = device_scan(c, A.emit, A.emit, n_maps, nullptr))) return mapres_fail(R, rc, true);
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL(lift_gather_kernel, dim3(per_wave), dim3(LIFT_NT), 0, c->stream, A);
+                e = hipGetLastError();
+            }
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&hinfo, info.p, sizeof(LiftInfo), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(&n_out, A.emit + n_maps, 4, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = main_wait(c); /* the one wait; the caller's table is free again */
+    if (e != hipSuccess) return mapres_fail(R, fail(c, NTL_EDEVICE, std::string("ntl_mapres_liftover: ") + hipGetErrorString(e)), true);
+    if (hinfo.err & LIFT_ERR_CTG) return mapres_fail(R, fail(c, NTL_EINVAL, "ntl_mapres_liftover: a mapping names a contig that the table does not hold (ctg >= n_ctg)"), true);
+    if (hinfo.err & LIFT_ERR_REGION) return mapres_fail(R, fail(c, NTL_EINTERNAL, "ntl_mapres_liftover: a mapping's hit region leaves the hit array"), true);
+    if (hinfo.err & LIFT_ERR_RANGE) return mapres_fail(R, fail(c, NTL_ERANGE, "ntl_mapres_liftover: a lifted position does not fit 32 bits"), true);
+    R->n_maps = n_out; R->n_hits = hinfo.n_hits;
+    *out = R.release();
     return NTL_OK;
 }
 
