@@ -230,6 +230,15 @@ uint64_t ntl_stitched_bytes(const ntl_stitched *s);
 int ntl_stitched_copy(const ntl_stitched *s, uint64_t lo, uint64_t hi, char *out);
 void ntl_stitched_destroy(ntl_stitched *s);
 
+/* Called bases per record of a stitched text, counted on the device (csrc/count_kernels.h; the work is divided by bytes): what
+ * `abyss-fac` reports of a FASTA file -- n:500, N50, sum -- needs nothing else of the text.  The caller cuts the text into n_rec
+ * records by rec_off[n_rec + 1], non-decreasing, inside the result; header lines and newlines are just more records, which it
+ * ignores.  out[i] = the number of bytes of [rec_off[i], rec_off[i + 1]) that are one of ACGTacgt (N, n, U and IUPAC codes are not
+ * called bases); an empty record counts 0, and so does every record when n_rec records cover no byte.  n_rec == 0 does nothing.
+ * NTL_EINVAL with a message: rec_off descends, or ends beyond the result.  The call WAITS: out is filled and rec_off free when it
+ * returns.  Event name for ntl_prof_get: "base_count" (the kernel). */
+int ntl_stitched_base_counts(const ntl_stitched *s, const uint64_t *rec_off, uint64_t n_rec, uint64_t *out);
+
 /* ---- sketch ---------------------------------------------------------------------------- */
 
 /* Asynchrony.  ntl_sketch_run[_indexed] and ntl_map_run only QUEUE device work and return; no size comes back to the host

@@ -22,6 +22,7 @@ SYMBOLS = [
     "ntl_batch_create", "ntl_batch_create_packed", "ntl_batch_create_packed_at", "ntl_packed_words", "ntl_batch_destroy", "ntl_batch_nseq", "ntl_batch_bases", "ntl_host_alloc", "ntl_host_free",
     "ntl_synth_genome", "ntl_synth_slices", "ntl_batch_download", "ntl_batch_mask", "ntl_batch_download_n",
     "ntl_ascii_create", "ntl_ascii_destroy", "ntl_ascii_nrec", "ntl_ascii_bytes", "ntl_stitch", "ntl_stitched_bytes", "ntl_stitched_copy", "ntl_stitched_destroy",
+    "ntl_stitched_base_counts",
     "ntl_sketch_run", "ntl_sketch_run_indexed", "ntl_sketch_run_for_map", "ntl_sketch_has_records", "ntl_sketch_destroy", "ntl_sketch_nseq", "ntl_sketch_count", "ntl_sketch_download",
     "ntl_sketch_strips", "ntl_sketch_redo_strips", "ntl_sketch_fallback_strips", "ntl_sketch_from_lists", "ntl_sketch_plan", "ntl_sketch_wait", "ntl_mapres_wait",
     "ntl_sketch_from_host", "ntl_overlap_filter", "ntl_overlap_cuts",
@@ -150,6 +151,7 @@ def load(path=None):
     L.ntl_stitched_copy.argtypes = [vp, C.c_uint64, C.c_uint64, vp]
     L.ntl_stitched_destroy.argtypes = [vp]
     L.ntl_stitched_destroy.restype = None
+    L.ntl_stitched_base_counts.argtypes = [vp, u64p, C.c_uint64, u64p]
     L.ntl_sketch_run.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(vp)]
     L.ntl_sketch_run_indexed.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
     L.ntl_sketch_run_for_map.argtypes = [vp, vp, C.c_int, C.c_int, vp, C.POINTER(vp)]
@@ -354,6 +356,17 @@ class Stitched(_Handle):
         """the whole text as a uint8 array"""
         n = self.nbytes
         return self.copy(0, n, np.empty(max(n, 1), np.uint8))[:n]
+
+    def base_counts(self, rec_off):
+        """Called bases per record (ntl_stitched_base_counts, csrc/count_kernels.h): rec_off = n + 1 ascending offsets into the text
+        -> u64[n], the bytes of [rec_off[i], rec_off[i + 1]) that are one of ACGTacgt.  Waits for the device."""
+        off = np.ascontiguousarray(rec_off, np.uint64)
+        if off.ndim != 1:
+            raise ValueError("rec_off must be one-dimensional")
+        n = max(len(off) - 1, 0)
+        out = np.zeros(n, np.uint64)
+        self.dev._chk(self.dev.L.ntl_stitched_base_counts(self.ptr, _ptr(off, C.c_uint64), n, _ptr(out, C.c_uint64)))
+        return out
 
 
 class Sketch(_Handle):

@@ -5,6 +5,7 @@
   ntlink_main       `ntLink pair target= reads= [k= w= ...]` make-style key=value    (ntLink:8-89,165)
   patch_gaps_main   `ntlink_patch_gaps.py ...` with the reference's argparse         (bin/ntlink_patch_gaps.py:760-784)
   overlap_sequences_main  `ntlink_overlap_sequences.py ...`, `-m` optional           (bin/ntlink_overlap_sequences.py:552-568)
+  merge_contigs_main  `MergeContigs [-k2] [-o FILE] [--stats FILE] FASTA PATH`       (ABySS, as ntLink:253-259 calls it)
 """
 import argparse
 import os
@@ -168,6 +169,45 @@ def overlap_sequences_main(argv=None):
         print(f"ERROR: {type(exc).__name__}: {exc}", file=sys.stderr)
         return 1
     print(datetime.datetime.today(), ": DONE!", flush=True)
+    return 0
+
+
+def merge_contigs_parser():
+    p = argparse.ArgumentParser(prog="MergeContigs", description="Merge the contigs of a path file into scaffolds (ABySS MergeContigs -k2, "
+                                                                 "as `ntLink scaffold` calls it)")
+    p.add_argument("-k", "--kmer", dest="k", help="k-mer size of the assembly: ntLink passes 2, and nothing else is implemented [2]", type=int, default=2)
+    p.add_argument("-o", "--out", dest="o", help="Output FASTA file [standard output]", type=str, default=None)
+    p.add_argument("--stats", help="Write the abyss-fac line of the output (n, n:500, L50, ..., sum) to this file", type=str, default=None)
+    p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    p.add_argument("fasta", metavar="FASTA", help="Contigs")
+    p.add_argument("path", metavar="PATH", help="Path file: name<TAB>node node ..., a node is <contig>+, <contig>- or <n>N")
+    return p
+
+
+def merge_contigs_main(argv=None):
+    """The merge stage (merge.merge_contigs): `MergeContigs [-k N] [-o FILE] [--stats FILE] FASTA PATH`, the scaffold FASTA on
+    standard output unless -o names a file.  Any error: a message, no output file left, exit status 1."""
+    ap = merge_contigs_parser()
+    a = ap.parse_args(argv)
+    if a.k != 2:
+        ap.error(f"-k {a.k}: only -k2, as ntLink calls MergeContigs, is implemented")
+    from . import merge
+    try:
+        dev = _device(a.device)
+        try:
+            if a.o is None:
+                sys.stdout.flush()
+            got = merge.merge_contigs(a.fasta, a.path, sys.stdout.fileno() if a.o is None else a.o, dev)
+        finally:
+            dev.close()
+        if a.stats:
+            with open(a.stats, "w") as fh:
+                fh.write(merge.fac_text(merge.fac_stats(got.counts), a.o or "-"))
+    except Exception as exc:
+        if a.o is not None and os.path.exists(a.o):
+            os.remove(a.o)
+        print(f"ERROR: {type(exc).__name__}: {exc}", file=sys.stderr)
+        return 1
     return 0
 
 

@@ -38,6 +38,7 @@
 #include "synth_kernels.h"
 #include "mask_kernels.h"
 #include "stitch_kernels.h"
+#include "count_kernels.h"
 #include "overlap_kernels.h"
 #include "overlap_cut_kernels.h"
 #include "format_kernels.h"
@@ -1107,6 +1108,41 @@ extern "C" void ntl_stitched_destroy(ntl_stitched *s)
     (void)hipSetDevice(s->c->device);
     if (s->queued) { (void)hipEventSynchronize(s->queued); s->c->pq.event_put(s->queued); } /* host_aux was the upload's source */
     delete s;
+}
+
+/* out[i] = the bytes of [rec_off[i], rec_off[i + 1]) of the text that are one of ACGTacgt (count_kernels.h).  Queued on MAIN behind
+ * the stitch; waits: out is filled and rec_off free when the call returns. */
+extern "C" int ntl_stitched_base_counts(const ntl_stitched *s, const uint64_t *rec_off, uint64_t n_rec, uint64_t *out)
+{
+    if (!s) return NTL_EINVAL;
+    ntl_ctx *c = s->c;
+    if (n_rec == 0) return NTL_OK;
+    if (!rec_off || !out) return fail(c, NTL_EINVAL, "rec_off and out are needed");
+    for (uint64_t i = 0; i < n_rec; i++)
+        if (rec_off[i + 1] < rec_off[i])
+            return fail(c, NTL_EINVAL, "rec_off descends at record " + std::to_string(i) + ": " + std::to_string(rec_off[i]) + " then " + std::to_string(rec_off[i + 1]));
+    if (rec_off[n_rec] > s->total)
+        return fail(c, NTL_EINVAL, "rec_off ends at " + std::to_string(rec_off[n_rec]) + ", beyond the result's " + std::to_string(s->total) + " bytes");
+    CountArgs A;
+    A.n_rec = n_rec; A.begin = rec_off[0]; A.end = rec_off[n_rec]; A.base = A.begin & ~15ull;
+    if (A.begin == A.end) { memset(out, 0, n_rec * sizeof(uint64_t)); return NTL_OK; }
+    const uint64_t tiles = (A.end - A.base + COUNT_TILE - 1) / COUNT_TILE;
+    if (tiles >= 0x7FFFFFFFull) return fail(c, NTL_EINVAL, "more text than one count call holds");
+    (void)hipSetDevice(c->device);
+    DevBuf d_off, d_out;
+    int rc;
+    if ((rc = d_off.alloc(c, (n_rec + 1) * 8)) || (rc = d_out.alloc(c, n_rec * 8))) return rc;
+    HIPCHK(c, hipMemcpyAsync(d_off.p, rec_off, (n_rec + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(d_out.p, 0, n_rec * 8, c->stream));
+    A.text = s->out.as<uint8_t>(); A.rec_off = d_off.as<uint64_t>(); A.out = d_out.as<unsigned long long>();
+    {
+        ProfSpan span(c, "base_count");
+        hipLaunchKernelGGL(base_count_kernel, dim3((unsigned)tiles), dim3(COUNT_NT), 0, c->stream, A);
+    }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, d_out.p, n_rec * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, main_wait(c));
+    return NTL_OK;
 }
 
 /* ------------------------------------------------------------------ sketch --------------- */

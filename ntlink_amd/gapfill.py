@@ -924,13 +924,16 @@ def print_gap_filled_sequences(pairs, sequences, scaffolds, reads, args, dev=Non
     return plan
 
 
-def write_stitched_records(dev, path, stores, records, max_bytes=STITCH_BYTES):
+def write_stitched_records(dev, path, stores, records, max_bytes=STITCH_BYTES, on_text=None):
     """Writes `path`: per record its header, its segments and a newline, assembled on the device (Device.stitch) from the resident
     `stores` (capi.Ascii).  records: (header bytes, [(store, rec, lo, hi, flags)], bytes of text) each; the headers of a call are
     one more store behind `stores`.  Whole records of at most max_bytes of text per call; the text comes back in pieces into
-    page-locked memory and goes to the file through ntl_write_blob.  The writer of the gap filler's and of the overlap stage's FASTA."""
+    page-locked memory and goes to the file through ntl_write_blob.  The writer of the gap filler's, the overlap stage's and the
+    merge stage's FASTA.  path: a file name, or a file descriptor that is open for writing (it stays open).  on_text(text, call):
+    called per stitch call with the capi.Stitched and the call's records while the text is on the device (the merge stage counts
+    its called bases there)."""
     newline = (capi.NTL_STITCH_FILL, ord("\n"), 0, 1, 0)
-    fd = os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
+    fd = path if isinstance(path, int) else os.open(path, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o666)
     buf = None
     try:
         for call in _stitch_calls(records, max_bytes):
@@ -942,6 +945,8 @@ def write_stitched_records(dev, path, stores, records, max_bytes=STITCH_BYTES):
             with dev.ascii([header for header, _segs, _size in call]) as headers, \
                     dev.stitch(list(stores) + [headers], np.array(segs, capi.STITCH_SEG_DT)) as text:
                 total = text.nbytes
+                if on_text is not None:
+                    on_text(text, call)
                 if buf is None or len(buf) < min(total, WRITE_PIECE):
                     dev.pinned_release(buf)
                     buf = dev.pinned_empty(min(total, WRITE_PIECE))
@@ -951,7 +956,8 @@ def write_stitched_records(dev, path, stores, records, max_bytes=STITCH_BYTES):
                     if dev.L.ntl_write_blob(fd, buf.ctypes.data, hi - lo) != 0:
                         raise OSError(f"{path}: write failed")
     finally:
-        os.close(fd)
+        if fd is not path:
+            os.close(fd)
         dev.pinned_release(buf)
 
 

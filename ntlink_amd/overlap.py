@@ -560,10 +560,12 @@ def read_fasta_file_trim_prep(resident):
 OUTPUT_SUFFIXES = (".trimmed_scafs.path", ".trimmed_scafs.tsv", ".trimmed_scafs.agp", ".trimmed_scafs.fa")
 
 
-def overlap_sequences(args, dev=None, batch_bases=BATCH_BASES):
+def overlap_sequences(args, dev=None, batch_bases=BATCH_BASES, with_resident=None):
     """main() of the reference behind its argument parser (:583-608): the whole overlap stage.  args: the reference's namespace (m f
     path fasta k d g outgap p v trim_info; it is not changed), m=None for the fused form.  Writes `args.p + ".trimmed_scafs.path"`
-    and `.fa`, with args.trim_info also `.tsv` and `.agp`; after a failure none of them is left.  -> (scaffolds, new paths)."""
+    and `.fa`, with args.trim_info also `.tsv` and `.agp`; after a failure none of them is left.  -> (scaffolds, new paths).
+    with_resident(scaffolds, resident): called once every file is written, while the contigs are still on the device (the merge
+    stage goes on from there: merge.merge_after_overlap); its failure is the stage's."""
     import copy
     from . import anchor, gapfill
     if getattr(args, "v", False):
@@ -582,6 +584,8 @@ def overlap_sequences(args, dev=None, batch_bases=BATCH_BASES):
                 print_trim_coordinates(args, scaffolds)
                 print_agp_file(new_paths, scaffolds, args)
             print_trimmed_scaffolds(args, scaffolds, resident=resident, dev=dev)
+            if with_resident is not None:
+                with_resident(scaffolds, resident)
     except BaseException:
         for suffix in OUTPUT_SUFFIXES:
             if os.path.exists(args.p + suffix):
