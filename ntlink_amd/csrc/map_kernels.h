@@ -13,7 +13,8 @@
  *                (:271-294) and print_paf (bin/ntlink_paf_output.py:9-135).  One wavefront per
  *                read; hit lists staged in LDS (global scratch for reads that do not fit);
  *                stream compaction with wave ballot + mbcnt prefix sums; run-level logic
- *                (a handful of runs per read) on lane 0.
+ *                (a handful of runs per read) on lane 0.  The first class maps four simple reads
+ *                at a time, one per group of 16 lanes (map_read_groups); what is not simple goes the way above.
  */
 #pragma once
 #include "dev_common.h"
@@ -168,6 +169,14 @@ struct PafRec { uint32_t read, ctg, q_start, q_end, t_start, t_end, n_hits, stra
 #define MAP_NRA 10   /* per-run u32 arrays of the global scratch form */
 #define MAP_NCLASS 3
 #define MAP_GROUP 8  /* consecutive reads a wavefront looks at per step (small: a batch of 50 k reads must still fill the device) */
+/* The group path of the first class (map_read_groups): a wavefront maps MAP_NG reads at a time, one per group of MAP_GW lanes, on
+   quarters of the class's staging -- 64 hits and 16 runs each.  16 lanes: a C3 read has 16 hits, and a group is one DPP row. */
+#define MAP_GW 16
+#define MAP_NG (MAP_NT / MAP_GW)
+#define MAP_GU 4     /* candidates a lane of a group loads per round, issued together: 64 per group, as the full wavefront's round */
+/* bits of MapSums::err raised here (bit 1 is GROUP_ERR_PROBE, group_kernels.h) */
+#define MAP_ERR_TWICE 1u        /* an accepted contig appeared twice in one read */
+#define MAP_ERR_LEFT_GROUP 4u   /* MapArgs::group_strict: a read of the first class left the group path */
 
 struct MapArgs {
     const uint32_t *rpos;   /* [minimizers] position in the read; the strand is bit 31 of the candidate's meta (EmitArgs::rpos) */
@@ -187,6 +196,8 @@ struct MapArgs {
        and every kernel here leaves the batch alone; the host makes the sketch again and queues the map a second time. */
     const uint32_t *mx_total;                     /* NULL: the count was known when the call was made */
     uint32_t mx_cap;
+    uint32_t lanes;                               /* lanes per read in the first class: MAP_GW (the group path), or MAP_NT: never entered (NTL_MAP_LANES) */
+    uint32_t group_strict;                        /* a first-class read that leaves the group path raises MAP_ERR_LEFT_GROUP (NTL_MAP_GROUP_STRICT) */
 };
 
 __device__ __forceinline__ bool map_sketch_overflowed(const MapArgs &A) { return A.mx_total && *A.mx_total > A.mx_cap; }
@@ -653,6 +664,147 @@ done:
     if (lane == 0) { A.n_maps[r] = R; A.n_hits[r] = n; A.n_pafs[r] = np; }
 }
 
+/* a group's 16 bits of a wavefront's ballot */
+__device__ __forceinline__ uint32_t map_group_bits(unsigned long long bal, uint32_t g) { return (uint32_t)(bal >> (MAP_GW * g)) & ((1u << MAP_GW) - 1u); }
+
+/* MAP_NG reads on one wavefront, one per group of MAP_GW lanes (r: the group's read, NTL_NONE: none), each on its quarter of the
+ * LDS arrays.  A group finishes a read on which nothing happens -- a SIMPLE read: at most MAP_CAPH / MAP_NG hits (after the z filter)
+ * in at most MAP_CAPR / MAP_NG runs, every run on a contig of its own (each is its own leader: no merge, nothing subsumed, every
+ * contig once), none noisy, every run's PAF record from the fast path (one hit, contig positions non-decreasing, or strictly
+ * decreasing) -- and writes what map_read would have written, word for word.  Any other read LEAVES before a word of it is
+ * written: its group's bit (lane MAP_GW * g) is set in the returned mask and the caller maps it with map_read, which stays
+ * the one statement of the reference's semantics.  Not entered with the repeat filter on.
+ * Every vote and hand-off is executed by all 64 lanes the same number of times (loop counts are the maximum over the groups, by a
+ * vote of their own); groups differ in predicates and in their slice of a ballot.  Only per-lane serial code diverges: a lane
+ * walking its run's hits. */
+template <int MAP_CAPH, int MAP_CAPR>
+__device__ __forceinline__ unsigned long long map_read_groups(const MapArgs &A, const uint32_t r, HitArr<uint16_t> H, RunArr<uint16_t> RU)
+{
+    constexpr uint32_t GCAPH = MAP_CAPH / MAP_NG, GCAPR = MAP_CAPR / MAP_NG;
+    static_assert(GCAPR <= MAP_GW, "a lane per run");
+    const uint32_t lane = threadIdx.x, g = lane / MAP_GW, l = lane % MAP_GW;
+    const uint32_t below = (1u << l) - 1u;
+    const bool act = r != NTL_NONE;
+    const uint32_t m0 = act ? A.mx_off[r] : 0u, nmx = act ? A.mx_off[r + 1] - m0 : 0u;
+    const int64_t rl = act ? (int64_t)A.read_len[r] : 0;
+    const MapParamsDev P = A.P;
+    uint32_t *const cf = H.cf + g * GCAPH, *const cpos = H.cpos + g * GCAPH, *const rpos = H.rpos + g * GCAPH;
+    uint32_t *const rctg = RU.ctg + g * GCAPR;
+    uint16_t *const rstart = RU.start + g * GCAPR;
+
+    /* bin/ntlink_pair.py:364-367 hits in read order; bin/ntlink_utils.py:206 contig length >= z */
+    uint32_t n = 0;
+    for (uint32_t c = 0; __ballot(c < nmx) != 0ull; c += MAP_GW * MAP_GU) {
+        Cand cd[MAP_GU];
+        uint32_t rp[MAP_GU];
+        bool v[MAP_GU];
+#pragma unroll
+        for (int u = 0; u < MAP_GU; u++) {
+            const uint32_t i = c + (uint32_t)u * MAP_GW + l;
+            cd[u].cpos = 0; cd[u].meta = 0; rp[u] = 0;
+            if (i < nmx) { cd[u] = A.cand[m0 + i]; rp[u] = A.rpos[m0 + i]; }
+        }
+#pragma unroll
+        for (int u = 0; u < MAP_GU; u++) {
+            v[u] = (cd[u].meta & 1u) != 0;
+            if (v[u]) v[u] = (int64_t)A.ctg_len[(cd[u].meta & 0x7FFFFFFFu) >> 2] >= (int64_t)P.z;
+        }
+#pragma unroll
+        for (int u = 0; u < MAP_GU; u++) {
+            const uint32_t gb = map_group_bits(__ballot(v[u]), g);
+            const uint32_t o = n + (uint32_t)__popc(gb & below);
+            if (v[u] && o < GCAPH) { /* (a read with more hits leaves: its count goes on, its stores stay in its quarter) */
+                const uint32_t meta = cd[u].meta & 0x7FFFFFFFu;
+                cf[o] = ((meta >> 2) << HF_CTG_SHIFT) | ((meta >> 1) & 1u) | ((cd[u].meta >> 31) << 1);
+                cpos[o] = cd[u].cpos; rpos[o] = rp[u];
+            }
+            n += (uint32_t)__popc(gb);
+        }
+    }
+    bool out = n > GCAPH; /* uniform in the group, as n and R are */
+    if (out) n = 0;
+    ntl_wave_sync();
+
+    /* runs: consecutive hits on one contig */
+    uint32_t R = 0;
+    for (uint32_t c = 0; __ballot(c < n) != 0ull; c += MAP_GW) {
+        const uint32_t i = c + l;
+        uint32_t cg = 0;
+        bool isb = false;
+        if (i < n) { cg = cf[i] >> HF_CTG_SHIFT; isb = i == 0 || cg != (cf[i - 1] >> HF_CTG_SHIFT); }
+        const uint32_t gb = map_group_bits(__ballot(isb), g);
+        const uint32_t q = R + (uint32_t)__popc(gb & below);
+        if (isb && q < GCAPR) { rstart[q] = (uint16_t)i; rctg[q] = cg; }
+        R += (uint32_t)__popc(gb);
+    }
+    if (R > GCAPR) out = true;
+    if (out) R = 0;
+    ntl_wave_sync();
+
+    /* lane q of the group walks run q */
+    bool bad = false, nd = true;
+    uint32_t s = 0, e = 0, ctg = 0, same = 0;
+    if (l < R) {
+        s = rstart[l]; e = l + 1 < R ? (uint32_t)rstart[l + 1] : n; ctg = rctg[l];
+        for (uint32_t j = 0; j < l; j++) bad |= rctg[j] == ctg; /* a contig in two runs: leader merge, subsumption */
+        bool sd = true;
+        uint32_t prev = cpos[s], mn = prev, mni = s, mx = prev, mxi = s;
+        for (uint32_t i = s; i < e; i++) {
+            const uint32_t p = cpos[i], f = cf[i];
+            same += (f & 1u) == ((f >> 1) & 1u) ? 1u : 0u;
+            nd = nd && prev <= p; sd = sd && (i == s || prev > p);
+            if (p < mn) { mn = p; mni = i; } /* first argmin */
+            if (p > mx) { mx = p; mxi = i; } /* first argmax */
+            prev = p;
+        }
+        /* bin/ntlink_utils.py:217-234 noisy contigs, as map_read has it */
+        if (e - s >= 2) {
+            const int64_t span = (int64_t)mx - (int64_t)mn;
+            if (P.x == 0.0) {
+                bad |= span > rl + P.k;
+            } else {
+                int64_t rd = (int64_t)rpos[mxi] - (int64_t)rpos[mni];
+                if (rd < 0) rd = -rd;
+                const double a = (double)(rl + P.k);
+                const double b = ntl_mul_add_rn(P.x, (double)rd, (double)P.k);
+                const double thr = b < a ? b : a;
+                bad |= (double)span > thr;
+            }
+        }
+        bad |= !(e - s == 1 || nd || sd); /* bin/ntlink_paf_output.py:95-101: anything else needs the rank sort */
+    }
+    if (map_group_bits(__ballot(bad), g) != 0u) out = true;
+
+    if (act && !out) {
+        /* bin/ntlink_pair.py:382-388 one record per accepted contig; bin/ntlink_paf_output.py:103-135 one line per run */
+        if (l < R) {
+            const uint32_t m = e - s;
+            MapRec M;
+            M.read = r; M.ctg = ctg; M.n_hits = m; M.pad = 0; M.hit_off = s;
+            A.maps[m0 + l] = M;
+            const uint32_t a = nd ? s : e - 1, b = nd ? e - 1 : s; /* first / last in ctg_pos order */
+            PafRec p;
+            p.read = r; p.ctg = ctg; p.n_hits = m; p.strand = 2 * same >= m ? 1u : 0u;
+            const uint32_t ca = cpos[a], cb = cpos[b], ra = rpos[a], rb = rpos[b];
+            p.t_start = ca < cb ? ca : cb; p.t_end = (ca > cb ? ca : cb) + (uint32_t)P.k;
+            p.q_start = ra < rb ? ra : rb; p.q_end = (ra > rb ? ra : rb) + (uint32_t)P.k;
+            A.pafs[m0 + l] = p;
+        }
+        for (uint32_t i = l; i < n; i += MAP_GW) {
+            HitRec h;
+            const uint32_t f = cf[i];
+            h.ctg_pos = cpos[i]; h.read_pos = rpos[i];
+            h.ctg_strand = (uint8_t)(f & 1u); h.read_strand = (uint8_t)((f >> 1) & 1u);
+            h.pad[0] = h.pad[1] = 0;
+            A.hits[m0 + i] = h;
+        }
+        if (l == 0) { A.n_maps[r] = R; A.n_hits[r] = n; A.n_pafs[r] = R; }
+    }
+    const bool left = act && out && l == 0;
+    if (left && A.group_strict) atomicOr(A.err, MAP_ERR_LEFT_GROUP);
+    return __ballot(left);
+}
+
 /* size class of a read by its number of minimizers (an upper bound of its hits) */
 __device__ __forceinline__ int map_class_of(uint32_t nmx) { return nmx <= 256u ? 0 : (nmx <= 512u ? 1 : 2); }
 
@@ -682,6 +834,25 @@ __global__ __launch_bounds__(MAP_NT) NTL_MAIN_STREAM_SGPRS void map_kernel(MapAr
         bool mine = false;
         if (lane < MAP_GROUP && r < A.nreads) mine = map_class_of(A.mx_off[r + 1] - A.mx_off[r]) == CLASS;
         unsigned long long bal = __ballot(mine);
+        if constexpr (CLASS == 0) if (A.lanes != MAP_NT && !A.P.repeat_filter) {
+            /* the group path: MAP_NG reads per round, one per group; what the groups leave is mapped below, a read at a time */
+            unsigned long long rest = 0ull;
+            while (bal) {
+                uint32_t jt[MAP_NG], mj = NTL_NONE;
+#pragma unroll
+                for (uint32_t t = 0; t < MAP_NG; t++) {
+                    jt[t] = bal ? (uint32_t)__ffsll((long long)bal) - 1u : NTL_NONE;
+                    bal &= bal - 1ull;
+                    if (lane / MAP_GW == t) mj = jt[t];
+                }
+                const unsigned long long left = map_read_groups<MAP_CAPH, MAP_CAPR>(A, mj == NTL_NONE ? NTL_NONE : (uint32_t)(base + mj), H, RU);
+#pragma unroll
+                for (uint32_t t = 0; t < MAP_NG; t++)
+                    if ((left >> (MAP_GW * t)) & 1ull) rest |= 1ull << jt[t];
+                ntl_wave_sync(); /* the staging arrays are reused by the next round */
+            }
+            bal = rest;
+        }
         while (bal) {
             const uint32_t j = (uint32_t)__ffsll((long long)bal) - 1u;
             bal &= bal - 1ull;

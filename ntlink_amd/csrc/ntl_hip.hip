@@ -2448,6 +2448,7 @@ static int map_prepare(ntl_ctx *c, ntl_mapres *R, MapWork &W)
     /* a sketch whose count is not known yet may have overflowed its arrays: the kernels look at its total and leave it alone */
     A.mx_total = reads->lz.pending ? &reads->sums.as<SketchSums>()->total_mx : nullptr;
     A.mx_cap = (uint32_t)std::min<uint64_t>(reads->cap, 0xFFFFFFFFull);
+    A.lanes = MAP_GW; A.group_strict = 0; /* (map_kernels_stage reads the knobs) */
     return NTL_OK;
 }
 
@@ -2487,11 +2488,16 @@ static int map_kernels_stage(ntl_ctx *c, const MapWork &W)
         const uint64_t resident = (uint64_t)std::max(1, atoi(e)) * (uint64_t)std::max(1, c->n_cu);
         g0 = std::min(g0, resident); g1 = std::min(g1, resident); g2 = std::min(g2, resident);
     }
-    hipLaunchKernelGGL((map_kernel<256, 64, 0>), dim3((unsigned)std::min<uint64_t>(groups, g0)), dim3(MAP_NT), 0, ms, W.A);
-    hipLaunchKernelGGL((map_kernel<512, 128, 1>), dim3((unsigned)std::min<uint64_t>(groups, g1)), dim3(MAP_NT), 0, ms, W.A);
-    hipLaunchKernelGGL((map_kernel<1024, 128, 2>), dim3((unsigned)std::min<uint64_t>(groups, g2)), dim3(MAP_NT), 0, ms, W.A);
+    MapArgs A = W.A;
+    /* NTL_MAP_LANES=64: the first class never enters its group path (one read per wavefront throughout: A/B runs, tests).
+       NTL_MAP_GROUP_STRICT=1: a first-class read that leaves the group path fails the result (MAP_ERR_LEFT_GROUP): which path ran */
+    if (const char *e = getenv("NTL_MAP_LANES")) if (atoi(e) == MAP_NT) A.lanes = MAP_NT;
+    if (const char *e = getenv("NTL_MAP_GROUP_STRICT")) A.group_strict = atoi(e) != 0;
+    hipLaunchKernelGGL((map_kernel<256, 64, 0>), dim3((unsigned)std::min<uint64_t>(groups, g0)), dim3(MAP_NT), 0, ms, A);
+    hipLaunchKernelGGL((map_kernel<512, 128, 1>), dim3((unsigned)std::min<uint64_t>(groups, g1)), dim3(MAP_NT), 0, ms, A);
+    hipLaunchKernelGGL((map_kernel<1024, 128, 2>), dim3((unsigned)std::min<uint64_t>(groups, g2)), dim3(MAP_NT), 0, ms, A);
     /* reads with more hits / runs than the largest staging holds (rare): same code on global scratch */
-    hipLaunchKernelGGL(map_overflow_kernel, dim3((unsigned)std::min<uint64_t>(W.nreads, 8192)), dim3(MAP_NT), 0, ms, W.A); /* no LDS: 32 wavefronts per CU resident */
+    hipLaunchKernelGGL(map_overflow_kernel, dim3((unsigned)std::min<uint64_t>(W.nreads, 8192)), dim3(MAP_NT), 0, ms, A); /* no LDS: 32 wavefronts per CU resident */
     HIPCHK(c, hipGetLastError());
     return NTL_OK;
 }
@@ -2539,7 +2545,9 @@ static const char *map_check(const PinSlot &slot, uint64_t, std::atomic<float> *
     const MapSums &hs = (const MapSums &)slot;
     if (hitf && hs.nmx) hitf->store((float)((double)hs.nfound / (double)hs.nmx), std::memory_order_relaxed);
     if (hs.err & GROUP_ERR_PROBE) return "a probe sequence of a grouped lookup did not end within its table (group_kernels.h)";
-    return hs.err ? "an accepted contig appeared twice in one read (bin/ntlink_utils.py:262-266)" : nullptr;
+    if (hs.err & MAP_ERR_TWICE) return "an accepted contig appeared twice in one read (bin/ntlink_utils.py:262-266)";
+    if (hs.err & MAP_ERR_LEFT_GROUP) return "a read of the first class left the group path (NTL_MAP_GROUP_STRICT, map_kernels.h map_read_groups)";
+    return hs.err ? "a map result's err word holds an unknown bit" : nullptr;
 }
 
 static void mapres_free(ntl_mapres *R)
