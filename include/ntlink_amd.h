@@ -40,6 +40,8 @@
  *   ntl_liftover  verbose mappings through an AGP   <- bin/ntlink_liftover_mappings.py:61-143 (ntLink_rounds:124-125)
  *   ntl_mapres_liftover  the same on a resident     <- liftover_ctg_mappings, print_adjusted_mappings (:61-121)
  *                 map result, on the device
+ *   ntl_mapres_pairs  the per-read part of the tally    <- tally_pairs_from_mappings, calculate_pair_info (bin/ntlink_pair.py:222-239,416-435)
+ *                 of a resident map result, on the device
  *
  * Conventions: every call returns 0 on success or a negative NTL_E* code; the message is
  * available from ntl_last_error().  All pointers in signatures are HOST pointers unless the
@@ -462,6 +464,41 @@ typedef struct {            /* one per contig number of the INPUT result's conti
 #define NTL_LIFT_LANE_LINES 16u
 int ntl_mapres_liftover(ntl_ctx *ctx, const ntl_mapres *in, const ntl_lift_entry *table, uint32_t n_ctg, int32_t k, ntl_mapres **out);
 
+/* The pair records of a resident result: the per-read part of ntl_tally_add (tally_pairs_from_mappings, calculate_pair_info,
+ * calculate_gap_size, normalize_pair of bin/ntlink_pair.py:157-239,416-435) on the device (csrc/pair_kernels.h), so that a result's
+ * tally needs neither its mappings nor its hits on the host.  One ntl_pair_rec per pair ntl_tally_add would record, in the order in
+ * which it would record them: src / tgt the contig numbers of the normalised pair (smaller name first; equal names swap), src_ori /
+ * tgt_ori 1 = '+', gap in 64 bits, anchor 1 iff both mappings have more than one hit, read the mappings' .read.  ntl_tally_add_pairs
+ * (below) does the rest -- the dictionary keyed by pair, which depends on the order across reads -- and leaves the tally as
+ * ntl_tally_add over the same reads leaves it.
+ *   ntl_pairtab   the device's copy of what the rules need of a tally: per contig the rank of its name and its length, plus k and f.
+ *                 Taken from the tally (copied: the tally may go), so that rank, k and f have one definition.  A table made on one
+ *                 context serves every context of the same device.  ntl_pairtab_create waits.
+ *   read_len      [n_reads], indexed by ntl_mapping.read -- or NULL: a read's length is then the largest read_pos among the first and
+ *                 last hits of its mappings, the checkpoint rule (bin/ntlink_pair.py:460-488), and n_reads is ignored
+ * A read is a run of consecutive mappings with equal .read; a mapping's first and last hit are read from its region, unused slots
+ * between regions are allowed (ntl_mapres_from_host), and a result that names a contig twice in one read is handled by key, as on the host.
+ * `r` is completed by the call, left alone, and may be destroyed afterwards.  One host wait in ntl_mapres_pairs, one in
+ * ntl_pairs_download (out[ntl_pairs_count()]).  The records' array is sized before their number is known, from the mappings and f: at
+ * most max(2, f / 2) records per mapping.  Event name for ntl_prof_get: "pairs".
+ * NTL_EINVAL with a message: a grouped result, a mapping whose ctg is beyond the table, a .read >= n_reads when read_len is given.
+ * NTL_ERANGE: an overhang of an evaluated pair is negative ("Gap distance estimation less than 0", reported at the wait), or the
+ * result would make 2^32 - 256 records or more.  No partial result in any of these cases -- ONE difference from the host path: where
+ * ntl_tally_add returns NTL_ERANGE the tally has already taken the pairs in front of the failing one; here nothing of that result is
+ * added.  The run aborts either way.
+ * NTL_PAIR_LANE_MAPS: a read of at most so many mappings is done by one lane, a longer one by a wavefront (the result is the same). */
+typedef struct { uint32_t src, tgt; int64_t gap; uint32_t read; uint8_t src_ori, tgt_ori, anchor, pad; } ntl_pair_rec;
+typedef struct ntl_tally ntl_tally;
+typedef struct ntl_pairtab ntl_pairtab;
+typedef struct ntl_pairs ntl_pairs;
+#define NTL_PAIR_LANE_MAPS 16u
+int ntl_pairtab_create(ntl_ctx *ctx, const ntl_tally *t, ntl_pairtab **out);
+void ntl_pairtab_destroy(ntl_pairtab *pt);
+int ntl_mapres_pairs(const ntl_mapres *r, const ntl_pairtab *pt, const uint32_t *read_len /* may be NULL */, uint64_t n_reads, ntl_pairs **out);
+uint64_t ntl_pairs_count(const ntl_pairs *p);
+int ntl_pairs_download(const ntl_pairs *p, ntl_pair_rec *out);
+void ntl_pairs_destroy(ntl_pairs *p);
+
 /* Grouped mapping: ntl_index_build + ntl_map_run once per group, on that group's contigs and reads alone, in one device pass -- the
  * gap filler's re-mapping loop (map_long_reads, bin/ntlink_patch_gaps.py:412-442: per gap one read piece against the minimizer dict
  * of the two scaffold ends around it, read_btllib_minimizers :397-410).  Group g = the contigs [ctg_group_off[g], ctg_group_off[g+1])
@@ -672,14 +709,17 @@ int ntl_write_blob(int fd, const char *p, uint64_t n);
  * in order (read_len indexed by ntl_mapping.read) and returns NTL_ERANGE where the reference
  * raises "Gap distance estimation less than 0".  ntl_tally_export lists every pair in order of
  * first appearance: contig indices, orientations (1 = '+'), anchor count and
- * gaps[gap_off[i] .. gap_off[i+1]) in read order (arrays sized from npairs / ngaps). */
-typedef struct ntl_tally ntl_tally;
+ * gaps[gap_off[i] .. gap_off[i+1]) in read order (arrays sized from npairs / ngaps).  (ntl_tally is declared with ntl_mapres_pairs.) */
 int ntl_tally_create(const char *ctg_names, const uint64_t *ctg_name_off, const uint32_t *ctg_len, uint64_t n_ctg,
                      int k, int f, ntl_tally **out);
 void ntl_tally_destroy(ntl_tally *t);
 int ntl_tally_add(ntl_tally *t, const ntl_mapping *maps, uint64_t n_maps, const ntl_hit *hits, const uint32_t *read_len);
 /* The same from the first and last hit of every mapping alone (ends[2 i], ends[2 i + 1]: ntl_text_download). */
 int ntl_tally_add_ends(ntl_tally *t, const ntl_mapping *maps, uint64_t n_maps, const ntl_hit *ends, const uint32_t *read_len);
+/* The same from the records ntl_mapres_pairs made of the mappings on the device, in their order: a new pair on first sight, the gap
+ * pushed, the anchor added.  After it the tally is what ntl_tally_add over the same reads leaves (ntl_tally_export gives equal arrays).
+ * NTL_EINVAL, with nothing added, for a contig number beyond the tally or an orientation above 1. */
+int ntl_tally_add_pairs(ntl_tally *t, const ntl_pair_rec *recs, uint64_t n);
 uint64_t ntl_tally_npairs(const ntl_tally *t);
 uint64_t ntl_tally_ngaps(const ntl_tally *t);
 int ntl_tally_export(const ntl_tally *t, uint32_t *src, uint8_t *src_ori, uint32_t *tgt, uint8_t *tgt_ori,

@@ -21,7 +21,7 @@ HEADER = os.path.join(os.path.dirname(HERE), "include", "ntlink_amd.h")
 # index_common.h did not rebuild ntl_hip.o, and objects travel to the GPU box)
 KERNEL_HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h"))
 # translation unit -> headers it depends on (besides include/ntlink_amd.h)
-UNITS = {"ntl_hip.hip": KERNEL_HEADERS, "ntl_io.cpp": [], "ntl_pairs.cpp": [], "ntl_liftover.cpp": []}
+UNITS = {"ntl_hip.hip": KERNEL_HEADERS, "ntl_io.cpp": [], "ntl_pairs.cpp": ["tally_view.h"], "ntl_liftover.cpp": []}
 SOURCES = list(UNITS) + KERNEL_HEADERS
 
 

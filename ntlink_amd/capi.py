@@ -38,6 +38,7 @@ SYMBOLS = [
     "ntl_liftover",
     "ntl_names_create", "ntl_names_destroy", "ntl_mapres_format", "ntl_text_sizes", "ntl_text_download", "ntl_text_destroy", "ntl_write_blob",
     "ntl_tally_add_ends", "ntl_tally_write", "ntl_io_errno",
+    "ntl_pairtab_create", "ntl_pairtab_destroy", "ntl_mapres_pairs", "ntl_pairs_count", "ntl_pairs_download", "ntl_pairs_destroy", "ntl_tally_add_pairs",
 ]
 
 MAPPING_DT = np.dtype([("read", "<u4"), ("ctg", "<u4"), ("n_hits", "<u4"), ("pad", "<u4"), ("hit_off", "<u8")])
@@ -60,6 +61,9 @@ NTL_OVERLAP_CUT, NTL_OVERLAP_GLOBAL, NTL_OVERLAP_LDS_SLICE, NTL_OVERLAP_SRC_MINU
 LIFT_ENTRY_DT = np.dtype([(nm, "<u4") for nm in ("new_ctg", "mode", "scaf_start", "ctg_start", "ctg_end")])  # ntl_lift_entry
 NTL_LIFT_ABSENT, NTL_LIFT_KEEP, NTL_LIFT_SHIFT, NTL_LIFT_MIRROR = 0, 1, 2, 3  # ntl_lift_entry.mode
 NTL_LIFT_LANE_LINES = 16
+PAIR_REC_DT = np.dtype([("src", "<u4"), ("tgt", "<u4"), ("gap", "<i8"), ("read", "<u4"), ("src_ori", "u1"), ("tgt_ori", "u1"), ("anchor", "u1"),
+                        ("pad", "u1")])  # ntl_pair_rec
+NTL_PAIR_LANE_MAPS = 16
 NO_CTG = 0xFFFFFFFF  # ntl_mapping.ctg of a name that is not in the reader's table
 
 
@@ -243,6 +247,16 @@ def load(path=None):
     L.ntl_tally_destroy.restype = None
     L.ntl_tally_add.argtypes = [vp, vp, C.c_uint64, vp, u32p]
     L.ntl_tally_add_ends.argtypes = [vp, vp, C.c_uint64, vp, u32p]
+    L.ntl_tally_add_pairs.argtypes = [vp, vp, C.c_uint64]
+    L.ntl_pairtab_create.argtypes = [vp, vp, C.POINTER(vp)]
+    L.ntl_pairtab_destroy.argtypes = [vp]
+    L.ntl_pairtab_destroy.restype = None
+    L.ntl_mapres_pairs.argtypes = [vp, vp, u32p, C.c_uint64, C.POINTER(vp)]
+    L.ntl_pairs_count.argtypes = [vp]
+    L.ntl_pairs_count.restype = C.c_uint64
+    L.ntl_pairs_download.argtypes = [vp, vp]
+    L.ntl_pairs_destroy.argtypes = [vp]
+    L.ntl_pairs_destroy.restype = None
     L.ntl_names_create.argtypes = [vp, vp, u64p, u32p, C.c_uint64, C.POINTER(vp)]
     L.ntl_names_destroy.argtypes = [vp]
     L.ntl_names_destroy.restype = None
@@ -511,6 +525,11 @@ class MapResult(_Handle):
 class NameTable(_Handle):
     """A name table (+ sequence lengths) resident on the device: the strings the text kernels copy into their lines."""
     _destroy = "ntl_names_destroy"
+
+
+class PairTable(_Handle):
+    """What the pair rules need of a tally, resident on the device (ntl_pairtab): name rank and length per contig, k and f."""
+    _destroy = "ntl_pairtab_destroy"
 
 
 class Text(_Handle):
@@ -872,6 +891,32 @@ class Device:
         p = C.c_void_p()
         self._chk(self.L.ntl_mapres_liftover(self.ptr, result.ptr, tb.ctypes.data if len(tb) else None, len(tb), int(k), C.byref(p)))
         return MapResult(self, p)
+
+    def pair_table(self, tally):
+        """The device's copy of what the pair rules need of `tally` (a pairing.PairTally): name rank and length per contig, k and f
+        (ntl_pairtab_create).  Serves every context of this GPU (Device.workers); the tally may go on being filled."""
+        p = C.c_void_p()
+        self._chk(self.L.ntl_pairtab_create(self.ptr, tally._h, C.byref(p)))
+        return PairTable(self, p)
+
+    def mapres_pairs(self, result, table, read_len=None):
+        """The pair records of `result`, made on the device (ntl_mapres_pairs, csrc/pair_kernels.h): a PAIR_REC_DT array with one record
+        per pair PairTally.add_batch would record for the same mappings, in its order -- what PairTally.add_pairs takes.  read_len is
+        indexed by the mappings' .read; None: a read's length is the largest read position among the first and last hits of its
+        mappings (the checkpoint rule).  No mapping and no hit comes to the host.  `result` is completed and left alone; it may belong
+        to another context of this GPU than `table`."""
+        dev = result.dev
+        rl = None if read_len is None else np.ascontiguousarray(read_len, np.uint32)
+        held = None if rl is None else rl if len(rl) else np.zeros(1, np.uint32)  # (an empty array is still "given": a pointer, n_reads = 0)
+        p = C.c_void_p()
+        dev._chk(dev.L.ntl_mapres_pairs(result.ptr, table.ptr, None if held is None else _ptr(held, C.c_uint32), 0 if rl is None else len(rl),
+                                        C.byref(p)))
+        try:
+            out = np.empty(int(dev.L.ntl_pairs_count(p)), PAIR_REC_DT)
+            dev._chk(dev.L.ntl_pairs_download(p, out.ctypes.data if len(out) else None))
+        finally:
+            dev.L.ntl_pairs_destroy(p)
+        return out
 
     def map_grouped(self, contig_sketch, ctg_len, ctg_group_off, read_sketch, read_len, read_group_off, k, z=1000, x=0.0, sensitive=False,
                     repeat_filter=False):

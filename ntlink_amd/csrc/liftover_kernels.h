@@ -185,14 +185,29 @@ __device__ __forceinline__ void lift_read_body(const LiftArgs &A, uint32_t m0, u
     if (hits) atomicAdd(&A.info->n_hits, hits);
 }
 
+/* A read = a run of consecutive mappings with equal .read.  The lines of the read from line m on, counted no further than limit + 1
+ * (limit + 1: "more than limit"). */
+__device__ __forceinline__ uint32_t read_lines_from(const MapRec *maps, uint32_t n_maps, uint32_t m, uint32_t limit)
+{
+    const uint32_t read = maps[m].read;
+    uint32_t L = 1u;
+    while (L <= limit && m + L < n_maps && maps[m + L].read == read) L++;
+    return L;
+}
+
+/* ... and 0 where line m is not a read's first line (the line before it names the same read) */
+__device__ __forceinline__ uint32_t read_lines_at_first(const MapRec *maps, uint32_t n_maps, uint32_t m, uint32_t limit)
+{
+    if (m && maps[m - 1u].read == maps[m].read) return 0u;
+    return read_lines_from(maps, n_maps, m, limit);
+}
+
 __global__ __launch_bounds__(LIFT_NT) void lift_read_kernel(LiftArgs A)
 {
     const uint32_t m = blockIdx.x * LIFT_NT + threadIdx.x;
     if (m >= A.n_maps) return;
-    const uint32_t read = A.maps[m].read;
-    if (m && A.maps[m - 1u].read == read) return; /* not a read's first line */
-    uint32_t L = 1u;
-    while (L <= LIFT_LANE_LINES && m + L < A.n_maps && A.maps[m + L].read == read) L++;
+    const uint32_t L = read_lines_at_first(A.maps, A.n_maps, m, LIFT_LANE_LINES);
+    if (!L) return; /* not a read's first line */
     if (L > LIFT_LANE_LINES) { A.over_list[atomicAdd(&A.info->n_over, 1u)] = m; return; }
     lift_read_body<false>(A, m, L, 0u);
 }
@@ -201,9 +216,8 @@ __global__ __launch_bounds__(64) void lift_read_overflow_kernel(LiftArgs A)
 {
     const uint32_t n_over = A.info->n_over; /* at most n_maps / (LIFT_LANE_LINES + 1) */
     for (uint32_t o = blockIdx.x; o < n_over && o < A.n_maps; o += gridDim.x) { /* uniform */
-        const uint32_t m = A.over_list[o], read = A.maps[m].read;
-        uint32_t L = 1u;
-        while (m + L < A.n_maps && A.maps[m + L].read == read) L++; /* uniform */
+        const uint32_t m = A.over_list[o];
+        const uint32_t L = read_lines_from(A.maps, A.n_maps, m, NTL_NONE); /* uniform */
         lift_read_body<true>(A, m, L, threadIdx.x);
         __syncthreads();
     }

@@ -43,6 +43,8 @@
 #include "overlap_cut_kernels.h"
 #include "format_kernels.h"
 #include "liftover_kernels.h"
+#include "pair_kernels.h"
+#include "tally_view.h"
 
 #define NTL_END_PAD 4096u /* bases of padding behind the last sequence (rolling over-reads) */
 #define SK_NT 256
@@ -3051,6 +3053,129 @@ extern "C" int ntl_mapres_liftover(ntl_ctx *c, const ntl_mapres *in, const ntl_l
     *out = R.release();
     return NTL_OK;
 }
+
+/* ------------------------------------------------------------------ pair records of a resident result ---- */
+
+static_assert(sizeof(ntl_pair_rec) == sizeof(PairRec) && sizeof(PairRec) == 24 && sizeof(PairLine) == 32 && sizeof(PairInfo) == 16 && sizeof(PairCtg) == 8,
+              "ABI record must match the device record");
+static_assert(NTL_PAIR_LANE_MAPS == PAIR_LANE_MAPS, "constant of the ABI and of pair_kernels.h");
+
+struct ntl_pairtab {
+    ntl_ctx *c;
+    uint64_t n_ctg = 0;
+    int32_t k = 0, f = 0;
+    DevBuf tab; /* PairCtg[n_ctg] */
+};
+
+struct ntl_pairs {
+    ntl_ctx *c;
+    uint64_t n = 0;
+    DevBuf recs; /* PairRec[n] (sized for the most the mappings could make) */
+};
+
+extern "C" int ntl_pairtab_create(ntl_ctx *c, const ntl_tally *t, ntl_pairtab **out)
+{
+    if (!c || !t || !out) return NTL_EINVAL;
+    *out = nullptr;
+    (void)hipSetDevice(c->device);
+    const TallyView V = ntl_tally_view(t);
+    std::unique_ptr<ntl_pairtab> pt(new ntl_pairtab());
+    pt->c = c; pt->n_ctg = V.n_ctg; pt->k = V.k; pt->f = V.f;
+    std::vector<PairCtg> host(V.n_ctg);
+    for (uint64_t i = 0; i < V.n_ctg; i++) host[i] = {V.rank[i], V.ctg_len[i]};
+    if (int rc = pt->tab.alloc(c, (V.n_ctg + 1) * sizeof(PairCtg))) return rc;
+    if (V.n_ctg) HIPCHK(c, hipMemcpyAsync(pt->tab.p, host.data(), V.n_ctg * sizeof(PairCtg), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, main_wait(c)); /* complete for every context of the device */
+    *out = pt.release();
+    return NTL_OK;
+}
+
+extern "C" void ntl_pairtab_destroy(ntl_pairtab *pt) { delete pt; }
+
+/* Three launches, the scan and two more launches on MAIN (pair_kernels.h), all sized by the result's counts, and ONE wait behind them:
+   the error word and the number of records come back together.  The records' array cannot wait for that number: it is sized from
+   what n_maps mappings could make at most -- per read of m lines m (m - 1) / 2 <= m * (f / 2) in the first branch (m <= f) and fewer
+   than 2 m in the second; never more than n_maps (n_maps - 1) / 2 in all.  Every temporary is a block of the context's cache. */
+extern "C" int ntl_mapres_pairs(const ntl_mapres *r, const ntl_pairtab *pt, const uint32_t *read_len, uint64_t n_reads, ntl_pairs **out)
+{
+    if (!r || !pt || !out) return NTL_EINVAL;
+    *out = nullptr;
+    ntl_ctx *c = r->c;
+    (void)hipSetDevice(c->device);
+    if (r->grouped) return fail(c, NTL_EINVAL, "ntl_mapres_pairs: a grouped result has no pair tally");
+    if (pt->c->device != c->device) return fail(c, NTL_EINVAL, "ntl_mapres_pairs: the table lives on another device");
+    if (n_reads > 0xFFFFFFFFull) return fail(c, NTL_EINVAL, "ntl_mapres_pairs: read numbers are 32 bits");
+    if (int frc = mapres_finalize(r)) return fail(c, frc, "ntl_mapres_pairs: the result failed: " + c->err);
+    const uint64_t n_maps = r->n_maps;
+    std::unique_ptr<ntl_pairs> P(new ntl_pairs());
+    P->c = c;
+    if (!n_maps) { *out = P.release(); return NTL_OK; }
+    const uint64_t per = pt->f < 0 ? n_maps : std::max<uint64_t>(2, (uint64_t)pt->f / 2);
+    const uint64_t cap = std::min<uint64_t>(std::min<uint64_t>(n_maps * std::min<uint64_t>(per, n_maps), n_maps * (n_maps - 1) / 2), PAIR_MAX_RECS);
+    DevBuf line, key1, words, info, rlen;
+    int rc;
+    if ((rc = P->recs.alloc(c, (cap + 1) * sizeof(PairRec))) || (rc = line.alloc(c, n_maps * sizeof(PairLine))) || (rc = key1.alloc(c, n_maps * 8)) ||
+        (rc = words.alloc(c, (2 * n_maps + 1) * 4)) || (rc = info.alloc(c, sizeof(PairInfo))) || (read_len && (rc = rlen.alloc(c, (n_reads + 1) * 4))))
+        return rc;
+    PairArgs A = {};
+    A.maps = r->maps.as<MapRec>(); A.hits = r->hits.as<HitRec>(); A.hits_cap = r->rec_cap;
+    A.n_maps = (uint32_t)n_maps; A.n_ctg = (uint32_t)pt->n_ctg; A.k = pt->k; A.f = pt->f;
+    A.table = pt->tab.as<PairCtg>(); A.read_len = read_len ? rlen.as<uint32_t>() : nullptr; A.n_reads = n_reads;
+    A.line = line.as<PairLine>(); A.key1 = key1.as<uint64_t>();
+    A.over_list = words.as<uint32_t>(); A.cnt = A.over_list + n_maps;
+    A.info = info.as<PairInfo>();
+    A.out = P->recs.as<PairRec>(); A.out_cap = cap;
+    PairInfo hinfo = {};
+    hipError_t e = hipSuccess;
+    {
+        ProfSpan sp(c, "pairs");
+        if (read_len && n_reads) e = hipMemcpyAsync(rlen.p, read_len, n_reads * 4, hipMemcpyHostToDevice, c->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(info.p, 0, sizeof(PairInfo), c->stream);
+        if (e == hipSuccess) {
+            const unsigned per_lane = (unsigned)((n_maps + PAIR_NT - 1) / PAIR_NT);
+            const unsigned over = (unsigned)std::min<uint64_t>(n_maps / (PAIR_LANE_MAPS + 1) + 1, PAIR_OVER_BLOCKS);
+            hipLaunchKernelGGL(pair_line_kernel, dim3(per_lane), dim3(PAIR_NT), 0, c->stream, A);
+            hipLaunchKernelGGL((pair_read_kernel<false>), dim3(per_lane), dim3(PAIR_NT), 0, c->stream, A);
+            hipLaunchKernelGGL((pair_read_overflow_kernel<false>), dim3(over), dim3(64), 0, c->stream, A);
+            e = hipGetLastError();
+            if (e == hipSuccess && (rc = device_scan(c, A.cnt, A.cnt, n_maps, nullptr))) return rc;
+            if (e == hipSuccess) {
+                hipLaunchKernelGGL((pair_read_kernel<true>), dim3(per_lane), dim3(PAIR_NT), 0, c->stream, A);
+                hipLaunchKernelGGL((pair_read_overflow_kernel<true>), dim3(over), dim3(64), 0, c->stream, A);
+                e = hipGetLastError();
+            }
+        }
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&hinfo, info.p, sizeof(PairInfo), hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = main_wait(c); /* the one wait; the caller's lengths are free again */
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(c->stream); /* the blocks return to the cache behind whatever still runs */
+        return fail(c, NTL_EDEVICE, std::string("ntl_mapres_pairs: ") + hipGetErrorString(e));
+    }
+    if (hinfo.err & PAIR_ERR_CTG) return fail(c, NTL_EINVAL, "ntl_mapres_pairs: a mapping names a contig that the table does not hold (ctg >= the tally's contigs)");
+    if (hinfo.err & PAIR_ERR_READ) return fail(c, NTL_EINVAL, "ntl_mapres_pairs: a mapping names a read that read_len does not hold (read >= n_reads)");
+    if (hinfo.err & PAIR_ERR_REGION) return fail(c, NTL_EINTERNAL, "ntl_mapres_pairs: a mapping without a hit, or one whose hit region leaves the hit array");
+    if (hinfo.err & PAIR_ERR_NEGATIVE) return fail(c, NTL_ERANGE, "ntl_mapres_pairs: Gap distance estimation less than 0");
+    if (hinfo.total >= PAIR_MAX_RECS) return fail(c, NTL_ERANGE, "ntl_mapres_pairs: the result makes 2^32 - 256 pair records or more");
+    P->n = hinfo.total;
+    *out = P.release();
+    return NTL_OK;
+}
+
+extern "C" uint64_t ntl_pairs_count(const ntl_pairs *p) { return p ? p->n : 0; }
+
+extern "C" int ntl_pairs_download(const ntl_pairs *p, ntl_pair_rec *out)
+{
+    if (!p || (p->n && !out)) return NTL_EINVAL;
+    ntl_ctx *c = p->c;
+    (void)hipSetDevice(c->device);
+    if (!p->n) return NTL_OK;
+    HIPCHK(c, hipMemcpyAsync(out, p->recs.p, p->n * sizeof(PairRec), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, main_wait(c));
+    return NTL_OK;
+}
+
+extern "C" void ntl_pairs_destroy(ntl_pairs *p) { delete p; }
 
 /* ------------------------------------------------------------------ text on the device ---- */
 

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/ntlink_amd.h"
+#include "tally_view.h"
 
 struct PairEntry {
     uint64_t key;
@@ -68,6 +69,22 @@ extern "C" int ntl_tally_create(const char *ctg_names, const uint64_t *ctg_name_
 }
 
 extern "C" void ntl_tally_destroy(ntl_tally *t) { delete t; }
+
+/* The dictionary step of add_pair (bin/ntlink_pair.py:322-334): a new pair on first sight, the gap pushed, the anchor added. */
+static void tally_record(ntl_tally *t, uint64_t key, uint32_t src, uint32_t tgt, int64_t gap, bool anchor)
+{
+    auto it = t->slot.find(key);
+    uint32_t e;
+    if (it == t->slot.end()) {
+        e = (uint32_t)t->pairs.size();
+        t->slot.emplace(key, e);
+        t->pairs.emplace_back();
+        t->pairs[e].key = key; t->pairs[e].src = src; t->pairs[e].tgt = tgt;
+    } else e = it->second;
+    t->pairs[e].gaps.push_back(gap);
+    t->ngaps++;
+    if (anchor) t->pairs[e].anchor++;
+}
 
 /* One batch of mappings (reads in order; read_len is indexed by ntl_mapping.read).  Returns NTL_ERANGE
  * when an overhang of an evaluated pair comes out negative -- the reference's "Gap distance estimation less than 0". */
@@ -119,17 +136,7 @@ static int tally_add(ntl_tally *t, const ntl_mapping *maps, uint64_t n_maps, con
                 const uint64_t key = ((uint64_t)t->rank[ci] << 33) | ((uint64_t)so << 32) | ((uint64_t)t->rank[cj] << 1) | to | (1ull << 63);
                 if ((gap < 0 ? -gap : gap) > rl) return 0;
                 if (check && check->count(key)) return 0;
-                auto it = t->slot.find(key);
-                uint32_t e;
-                if (it == t->slot.end()) {
-                    e = (uint32_t)t->pairs.size();
-                    t->slot.emplace(key, e);
-                    t->pairs.emplace_back();
-                    t->pairs[e].key = key; t->pairs[e].src = ci; t->pairs[e].tgt = cj;
-                } else e = it->second;
-                t->pairs[e].gaps.push_back(gap);
-                t->ngaps++;
-                if (maps[i].n_hits > 1 && maps[j].n_hits > 1) t->pairs[e].anchor++;
+                tally_record(t, key, ci, cj, gap, maps[i].n_hits > 1 && maps[j].n_hits > 1);
                 return key;
             };
             if (m <= (uint64_t)t->f) {
@@ -160,6 +167,26 @@ extern "C" int ntl_tally_add(ntl_tally *t, const ntl_mapping *maps, uint64_t n_m
 extern "C" int ntl_tally_add_ends(ntl_tally *t, const ntl_mapping *maps, uint64_t n_maps, const ntl_hit *ends, const uint32_t *read_len)
 {
     return tally_add<true>(t, maps, n_maps, ends, read_len);
+}
+
+/* The records ntl_mapres_pairs made of a result (pair_kernels.h), in its order: the per-read part of tally_add is done, what is left
+ * is the dictionary.  Nothing is added unless every record is good. */
+extern "C" int ntl_tally_add_pairs(ntl_tally *t, const ntl_pair_rec *recs, uint64_t n)
+{
+    if (!t || (n && !recs)) return NTL_EINVAL;
+    for (uint64_t i = 0; i < n; i++)
+        if (recs[i].src >= t->rank.size() || recs[i].tgt >= t->rank.size() || recs[i].src_ori > 1 || recs[i].tgt_ori > 1) return NTL_EINVAL;
+    for (uint64_t i = 0; i < n; i++) {
+        const ntl_pair_rec &r = recs[i];
+        const uint64_t key = ((uint64_t)t->rank[r.src] << 33) | ((uint64_t)r.src_ori << 32) | ((uint64_t)t->rank[r.tgt] << 1) | r.tgt_ori | (1ull << 63);
+        tally_record(t, key, r.src, r.tgt, r.gap, r.anchor != 0);
+    }
+    return NTL_OK;
+}
+
+TallyView ntl_tally_view(const ntl_tally *t)
+{
+    return {t->rank.data(), t->ctg_len.data(), (uint64_t)t->ctg_len.size(), t->k, t->f};
 }
 
 extern "C" uint64_t ntl_tally_npairs(const ntl_tally *t) { return t ? t->pairs.size() : 0; }

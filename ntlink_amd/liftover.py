@@ -99,7 +99,9 @@ def lift_table(agp_dict, contig_names):
 
 def lift_result(result, agp_dict, contig_names, k, dev):
     """A resident capi.MapResult whose contig numbers index `contig_names`, lifted through the AGP on the device.  -> (the new
-    MapResult, the output names its contig numbers index).  `result` is completed and left alone."""
+    MapResult, the output names its contig numbers index).  `result` is completed and left alone.  The next round's tally of the lifted
+    result needs none of its records on the host: dev.mapres_pairs(lifted, dev.pair_table(tally)) with a PairTally over the output
+    names gives the pair records (read_len=None: the checkpoint rule), and tally.add_pairs takes them."""
     table, out_names = lift_table(agp_dict, contig_names)
     return dev.mapres_liftover(result, table, k), out_names
 
@@ -114,7 +116,8 @@ def _unknown_contig(mappings_filename, known):
     return "?"
 
 
-def liftover_mappings_device(mappings_filename, agp_dict, output, k, dev, contig_names=None, tally=None, max_bytes=256 << 20):
+def liftover_mappings_device(mappings_filename, agp_dict, output, k, dev, contig_names=None, tally=None, max_bytes=256 << 20,
+                             device_tally=False):
     """`liftover_mappings` on the device `dev` (capi.Device): blocks of whole reads of about max_bytes of text (formats.read_verbose)
     become resident results (mapres_from_host), are lifted there (mapres_liftover), and the lines the device's formatter makes of them
     are written block by block (ntl_write_blob) to a temporary file beside `output`, which takes its name when it is complete; on
@@ -124,6 +127,8 @@ def liftover_mappings_device(mappings_filename, agp_dict, output, k, dev, contig
     (sequences the overlap stage left out, say) lists them too.  tally: a pairing.PairTally over the OUTPUT names (lift_table gives
     them): every block's mappings and first / last hits go to it as well (ntl_tally_add_ends, the read length being the largest mapped
     read position as in the checkpoint path, bin/ntlink_pair.py:460-488) -- the next round's tally without reading the lifted file.
+    device_tally: with `tally`, the lifted result's pair records are made on the device instead (Device.mapres_pairs with
+    read_len=None, which is that rule) and the tally takes them with add_pairs: the same tally.
 
     Two differences from the host path, which never parses the tokens of a contig that is not in the AGP and needs no name table:
     a line that names a contig which is neither in the AGP nor in contig_names raises ValueError naming it, and a malformed token
@@ -135,6 +140,7 @@ def liftover_mappings_device(mappings_filename, agp_dict, output, k, dev, contig
     lines_in = lines_out = 0
     no_pafs = np.zeros(0, capi.PAF_DT)
     fd = os.open(tmp, os.O_WRONLY | os.O_CREAT | os.O_TRUNC, 0o644)
+    pair_tab = dev.pair_table(tally) if tally is not None and device_tally else None
     try:
         with dev.names(out_names, np.zeros(len(out_names), np.uint32)) as cn:
             for block in formats.read_verbose(str(mappings_filename), names, max_bytes=max_bytes, lib_path=dev.lib_path):
@@ -146,11 +152,14 @@ def liftover_mappings_device(mappings_filename, agp_dict, output, k, dev, contig
                 with dev.mapres_from_host(block.maps, block.hits, no_pafs) as res, dev.mapres_liftover(res, table, k) as lifted, \
                         dev.names(block.names, np.zeros(n_reads, np.uint32)) as rn, lifted.format(rn, cn, True, False) as text:
                     d = text.download()
+                    recs = dev.mapres_pairs(lifted, pair_tab) if pair_tab is not None else None
                 try:
                     if len(d["verbose"]) and dev.L.ntl_write_blob(fd, d["verbose"].ctypes.data, len(d["verbose"])) != 0:
                         raise OSError(f"writing {tmp} failed")
                     lines_out += len(d["maps"])
-                    if tally is not None and len(d["maps"]):
+                    if recs is not None:
+                        tally.add_pairs(recs)
+                    elif tally is not None and len(d["maps"]):
                         read_len = np.zeros(n_reads, np.uint32)
                         np.maximum.at(read_len, d["maps"]["read"], np.maximum(d["ends"]["read_pos"][0::2], d["ends"]["read_pos"][1::2]))
                         tally.add_batch_ends(d["maps"], d["ends"], read_len)
@@ -165,6 +174,9 @@ def liftover_mappings_device(mappings_filename, agp_dict, output, k, dev, contig
         if os.path.exists(tmp):
             os.remove(tmp)
         raise
+    finally:
+        if pair_tab is not None:
+            pair_tab.close()
     return lines_in, lines_out
 
 

@@ -1,7 +1,9 @@
 """Host tail of the pair stage: contig-pair tally, filters, `.pairs.tsv`, `.scaffold.dot`.
 
-Stays on the CPU by design (BASELINE.json north_star: "scaffold-graph ... stay on CPU"); it consumes
-the mapping records the GPU produced.  Behaviour restated from bin/ntlink_pair.py:
+Stays on the CPU by design (BASELINE.json north_star: "scaffold-graph ... stay on CPU"): the dictionary keyed by
+pair, the two filters and the two writers.  The per-read part of the tally runs on the host over the mapping records the
+GPU produced, or -- `PairTally.add_pairs` -- on the device, where the records lie (csrc/pair_kernels.h).  Behaviour
+restated from bin/ntlink_pair.py:
   tally_pairs_from_mappings :416-435   add_pair :315-334   calculate_pair_info :222-239
   calculate_gap_size :157-187          normalize_pair :213-219   PairInfo :58-83
   filter_pairs_distances :247-255      filter_weak_anchor_pairs :241-244   write_pairs :490-496
@@ -74,6 +76,18 @@ class PairTally:
             raise AssertionError("Gap distance estimation less than 0")  # bin/ntlink_pair.py:173-184
         if rc != 0:
             raise ValueError(f"ntl_tally_add failed with {rc}")
+
+    def add_pairs(self, recs):
+        """The same from the pair records the device made of a result (capi.Device.mapres_pairs, PAIR_REC_DT): what is left of the
+        tally for the host is the dictionary (ntl_tally_add_pairs)."""
+        from . import capi
+        recs = np.ascontiguousarray(recs, capi.PAIR_REC_DT)
+        self._pairs = None
+        rc = self._L.ntl_tally_add_pairs(self._h, recs.ctypes.data if len(recs) else None, len(recs))
+        if rc == -5:
+            raise AssertionError("Gap distance estimation less than 0")
+        if rc != 0:
+            raise ValueError(f"ntl_tally_add_pairs failed with {rc}")
 
     def export(self):
         """(src u32, src_ori u8, tgt u32, tgt_ori u8, anchor u32, gap_off u64[n+1], gaps i64): every pair in order of

@@ -40,9 +40,12 @@ def _log(*a):
 class PairOutputs:
     """<prefix>.verbose_mapping.tsv / .paf writers + the pair tally, fed batch by batch in read order."""
 
-    def __init__(self, prefix, ctg_names, ctg_len, k, f, verbose, paf, part=""):
-        """part: suffix of this rank's part files in a multi-process run (the final names appear by a rename at the end)"""
+    def __init__(self, prefix, ctg_names, ctg_len, k, f, verbose, paf, part="", device_tally=False):
+        """part: suffix of this rank's part files in a multi-process run (the final names appear by a rename at the end)
+        device_tally: the batches bring their pair records, made on the device (capi.Device.mapres_pairs; NTL_DEVICE_TALLY=1 where the
+        drivers construct this): `add` takes res["pairs"], and a batch of a run that wants neither file is nothing but that array"""
         self.prefix, self.part = prefix, part
+        self.device_tally = bool(device_tally)
         self.ctg_names, self.ctg_len = ctg_names, ctg_len
         self.verbose_fh = open(prefix + ".verbose_mapping.tsv" + part, "w") if verbose else None
         self.paf_fh = open(prefix + ".paf" + part, "w") if paf else None
@@ -50,8 +53,20 @@ class PairOutputs:
         self.t_write = self.t_tally = 0.0
         self._exc = None
 
+    def _tally_batch(self, res, read_len):
+        if "pairs" in res:
+            self.tally.add_pairs(res["pairs"])
+        elif "ends" in res:
+            self.tally.add_batch_ends(res["maps"], res["ends"], read_len)
+        else:
+            self.tally.add_batch(res, read_len)
+
     def add(self, res, read_names, read_len):
         t0 = time.perf_counter()
+        if "pairs" in res and "maps" not in res:  # neither file is wanted: the pair records are all the batch brought
+            self.tally.add_pairs(res["pairs"])
+            self.t_tally += time.perf_counter() - t0
+            return
         if "verbose" in res:  # the lines were made on the device (capi.MapResult.format): they are written as they are
             paf_job = None
             if self.paf_fh and len(res["paf"]):
@@ -62,7 +77,7 @@ class PairOutputs:
                 if self.verbose_fh:
                     formats.write_blob(self.verbose_fh, res["verbose"])
                 t1 = time.perf_counter()
-                self.tally.add_batch_ends(res["maps"], res["ends"], read_len)
+                self._tally_batch(res, read_len)
             finally:
                 if paf_job:
                     paf_job.join()
@@ -82,7 +97,7 @@ class PairOutputs:
             if self.verbose_fh:
                 formats.write_verbose(self.verbose_fh, res, read_names, self.ctg_names)
             t1 = time.perf_counter()
-            self.tally.add_batch(res, read_len)
+            self._tally_batch(res, read_len)
         finally:
             if paf_job:
                 paf_job.join()
@@ -533,13 +548,15 @@ def _append_part(final_path, part_path, offset):
     os.remove(part_path)
 
 
-def _map_batches(dev, ix, batches, drain, stats, t_mark, w, first=None, text=None, **map_kw):
+def _map_batches(dev, ix, batches, drain, stats, t_mark, w, first=None, text=None, pairs=None, records=True, **map_kw):
     """The device stage of the pair driver: read batches -> records, handed to `drain` in input order.
 
     NTL_DEVICE_STREAMS (default 2) worker threads, each with its own context on the GPU (stream, block cache, page-locked
     result buffers), take batches in turn: while one batch's kernels and record download run, the next batch's bases
     cross PCIe.  The batches' results are committed in input order.  `first` (if given) runs on the calling thread, on `dev`,
-    once the other workers have started: work of the contig stage that the mapping does not depend on."""
+    once the other workers have started: work of the contig stage that the mapping does not depend on.  `pairs` (a capi.PairTable):
+    every batch also brings its pair records, made on the device; with records=False it brings nothing else -- no text is made and no
+    mapping or hit is downloaded."""
     import threading
     n_workers = max(1, int(os.environ.get("NTL_DEVICE_STREAMS", "2")))
     devs = [dev] + dev.workers(n_workers)  # kept by `dev` from one call to the next
@@ -581,8 +598,8 @@ def _map_batches(dev, ix, batches, drain, stats, t_mark, w, first=None, text=Non
                         t_sk = time.perf_counter()
                         with wdev.map(ix, rsk, rl, **map_kw) as res:
                             t_mp = time.perf_counter()
-                            pres = None
-                            if text is not None:  # (contig name table, verbose, paf): the lines are formatted on the device
+                            pres = None if records else {}
+                            if records and text is not None:  # (contig name table, verbose, paf): the lines are formatted on the device
                                 try:
                                     with wdev.names(rs_.names, rl) as rn, res.format(rn, text[0], text[1], text[2]) as txt:
                                         pres = txt.download()
@@ -591,6 +608,8 @@ def _map_batches(dev, ix, batches, drain, stats, t_mark, w, first=None, text=Non
                                         raise
                             if pres is None:
                                 pres = res.download(pinned=True)
+                            if pairs is not None:
+                                pres["pairs"] = wdev.mapres_pairs(res, pairs, rl)
                             n_mx, n_hit = rsk.count, res.n_index_hits
                 t_done = time.perf_counter()
                 _mark("dev_done", seq)
@@ -644,8 +663,12 @@ def _map_batches(dev, ix, batches, drain, stats, t_mark, w, first=None, text=Non
 
 def run_pair(dev, target, reads, prefix=None, k=32, w=100, n=1, a=1, z=1000, f=10, x=0.0, paf=False, verbose=True,
              sensitive=False, repeats=False, pairs_tsv=False, batch_bases=DEFAULT_BATCH_BASES, write_contig_tsv=True,
-             comm=None):
+             comm=None, device_tally=None):
     """`ntLink pair target=T reads='R1 R2' k= w= ...`: the fused device path.
+
+    device_tally (None: NTL_DEVICE_TALLY=1 turns it on; the default is off): every batch's pair records are made on the device
+    (capi.Device.mapres_pairs) and the host keeps the dictionary only; with verbose=False paf=False no text is made and no mapping or
+    hit leaves the device.  The outputs are the same bytes either way.
 
     With a communicator of world > 1 (one process per GPU) every rank builds the same contig index on its own GPU and
     owns a contiguous BYTE RANGE of the concatenated read files (seqio.shard_plan): it parses only that, maps it, formats
@@ -693,7 +716,9 @@ def run_pair(dev, target, reads, prefix=None, k=32, w=100, n=1, a=1, z=1000, f=1
     # place -- a run that dies half way leaves no well-formed <prefix>.verbose_mapping.tsv with a fraction of the reads,
     # which the next run (this driver and the reference alike, bin/ntlink_pair.py:565-567) would take for a checkpoint.
     part = "" if comm.world == 1 else f".part{comm.rank}"
-    out = PairOutputs(prefix, ctg.names, ctg_len, k, f, verbose, paf, part=part)
+    if device_tally is None:
+        device_tally = os.environ.get("NTL_DEVICE_TALLY", "0") == "1"
+    out = PairOutputs(prefix, ctg.names, ctg_len, k, f, verbose, paf, part=part, device_tally=device_tally)
 
     def consume(pres, names, lens):
         _mark("write_start")
@@ -736,13 +761,17 @@ def run_pair(dev, target, reads, prefix=None, k=32, w=100, n=1, a=1, z=1000, f=1
                         stats["t_contigs_parts"]["download_for_tsv_beside_mapping"] = round(time.perf_counter() - t0, 4)
                     # NTL_DEVICE_TEXT=0: records cross PCIe and the host's emitter threads format them (ntl_write_verbose / _paf)
                     ctg_tab = dev.names(ctg.names, ctg_len) if os.environ.get("NTL_DEVICE_TEXT", "1") != "0" else None
+                    pair_tab = dev.pair_table(out.tally) if out.device_tally else None
                     try:
                         _map_batches(dev, ix, batches, drain, stats, t_mark, w, first=contig_tsv if tsv_drain else None,
                                      text=(ctg_tab, verbose, paf) if ctg_tab is not None else None,
+                                     pairs=pair_tab, records=bool(verbose or paf or pair_tab is None),
                                      k=k, z=z, x=x, sensitive=sensitive, repeat_filter=repeats)
                     finally:
                         if ctg_tab is not None:
                             ctg_tab.close()
+                        if pair_tab is not None:
+                            pair_tab.close()
         t_fin = time.perf_counter()
         drain.close()
         if tsv_drain:
