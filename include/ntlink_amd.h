@@ -64,6 +64,9 @@
  * (the threshold pass without staged keys for the large windows too), NTL_EMIT_U=2 (a kernel variant kept for the record; the
  * NTL_SKETCH_LANES experiment's code has left the tree, profiles/HISTORY.md 4.12 is its record), NTL_PIPELINE=0 (one stream per context; default: a second stream for
  * the window stage), NTL_PIPELINE_PRIO (0 no stream priorities, 1 = default: MAIN above the window stream, 2 the reverse),
+ * NTL_SIDE_STREAM (1: a third stream for the window stage's give-up passes, beside the next sketch's window kernel; 2: a sketch's
+ * preparation on it too; default 0: both stay on the window stream; NTL_SIDE_PRIO=0: that stream at the window stream's priority
+ * instead of MAIN's),
  * NTL_SKETCH_CAP_GUESS (records a sketch's arrays hold before its count is known; tests force the second round with it).
  */
 #ifndef NTLINK_AMD_H
@@ -107,6 +110,9 @@ int ntl_ctx_pipelined(const ntl_ctx *ctx);
 /* Turns the second stream off / on again at a quiet point (waits for everything queued first).  NTL_EINVAL when the
  * context was created under NTL_PIPELINE=0. */
 int ntl_ctx_set_pipeline(ntl_ctx *ctx, int on);
+/* 1 while what follows a sketch's first window kernel -- the passes over the strips it gave up -- is queued on a third stream of the
+ * context, beside the next sketch's window kernel: a pipelined context that was created under NTL_SIDE_STREAM=1 (or 2). */
+int ntl_ctx_side_stream(const ntl_ctx *ctx);
 
 /* Kernel timing with HIP events on the context's stream.  When enabled, every launch of the
  * named kernel groups is bracketed by events; ntl_prof_get returns the accumulated time and

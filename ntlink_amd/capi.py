@@ -17,7 +17,7 @@ DEFAULT_LIB = os.path.join(_HERE, "libntlink_hip.so")
 
 # every symbol include/ntlink_amd.h declares
 SYMBOLS = [
-    "ntl_ctx_create", "ntl_ctx_destroy", "ntl_last_error", "ntl_ctx_device_name", "ntl_ctx_sync", "ntl_ctx_pipelined", "ntl_ctx_set_pipeline",
+    "ntl_ctx_create", "ntl_ctx_destroy", "ntl_last_error", "ntl_ctx_device_name", "ntl_ctx_sync", "ntl_ctx_pipelined", "ntl_ctx_set_pipeline", "ntl_ctx_side_stream",
     "ntl_prof_enable", "ntl_prof_reset", "ntl_prof_get",
     "ntl_batch_create", "ntl_batch_create_packed", "ntl_batch_create_packed_at", "ntl_packed_words", "ntl_batch_destroy", "ntl_batch_nseq", "ntl_batch_bases", "ntl_host_alloc", "ntl_host_free",
     "ntl_synth_genome", "ntl_synth_slices", "ntl_batch_download", "ntl_batch_mask", "ntl_batch_download_n",
@@ -120,6 +120,7 @@ def load(path=None):
     L.ntl_ctx_sync.argtypes = [vp]
     L.ntl_ctx_pipelined.argtypes = [vp]
     L.ntl_ctx_set_pipeline.argtypes = [vp, C.c_int]
+    L.ntl_ctx_side_stream.argtypes = [vp]
     L.ntl_sketch_wait.argtypes = [vp]
     L.ntl_mapres_wait.argtypes = [vp]
     L.ntl_prof_enable.argtypes = [vp, C.c_int]
@@ -623,6 +624,11 @@ class Device:
     @property
     def pipelined(self):
         return bool(self.L.ntl_ctx_pipelined(self.ptr))
+
+    @property
+    def side_stream(self):
+        """The window stage's give-up passes run on a third stream (pipelined contexts made under NTL_SIDE_STREAM=1 or 2)."""
+        return bool(self.L.ntl_ctx_side_stream(self.ptr))
 
     def set_pipeline(self, on):
         """Window stage on its own stream (on) or behind everything else on the one stream (off); drains the device first."""

@@ -1,8 +1,10 @@
 /*
  * The device block allocator of a context: host code over the HIP runtime, nothing of the context in it.
  *   take / give             the stream-ordered block cache: a block goes back while kernels that use it may still be queued, and is handed
- *                           out again to work queued BEHIND them on the same stream (no wait); one that was used on both streams goes back
- *                           with an event per stream, and whoever takes it next must not run ahead of the other stream's.
+ *                           out again to work queued BEHIND them on the same stream (no wait); one that was used on several streams goes
+ *                           back with an event per stream, and whoever takes it next must not run ahead of the other streams'.
+ *   streams                 MAIN, the window stage's (WINDOW) and the side stream of its give-up passes (SIDE); a stream that is not there
+ *                           (one-stream contexts, no side stream) counts as the one in front of it: SIDE as WINDOW, WINDOW as MAIN.
  *   alloc_ / free_uncached  what the cache is filled from: blocks up to SLAB_MAX_REQ are cut from slabs of SLAB_BYTES (a hipMalloc costs
  *                           4-9 ms of host time whatever its size, and a context's first read batch asked for seventy: 0.6 s per context of
  *                           a process's first pass, profiles/r04_first_pass.txt); larger ones are the driver's own.
@@ -21,37 +23,45 @@
 #include <vector>
 
 struct DevPool {
-    enum { MAIN = 0, WINDOW = 1, NSID = 2 };
+    enum { MAIN = 0, WINDOW = 1, SIDE = 2, NSID = 3 };
     static constexpr int OK = 0, NOMEM = -3; /* NTL_OK, NTL_ENOMEM of include/ntlink_amd.h */
     static constexpr size_t SLAB_BYTES = (size_t)1 << 30, SLAB_MAX_REQ = (size_t)192 << 20;
     /* the cache's misses that reached the driver, and their host time: ntl_prof_get(ctx, "hipMalloc") -- what a process's first pass pays once */
     uint64_t driver_allocs = 0;
     double driver_ms = 0;
 
-    /* window == main: one stream, every request is MAIN's.  cache_bound: upper bound of the bytes the cache holds. */
-    void setup(hipStream_t main, hipStream_t window, size_t cache_bound, bool slabs)
+    /* window == main: one stream, every request is MAIN's; side == NULL: none, its requests are WINDOW's.  cache_bound: upper bound of
+       the bytes the cache holds. */
+    void setup(hipStream_t main, hipStream_t window, size_t cache_bound, bool slabs, hipStream_t side = nullptr)
     {
-        st[MAIN] = main; st[WINDOW] = window;
+        st[MAIN] = main; st[WINDOW] = window; st[SIDE] = window != main ? side : nullptr;
         pool_cap = cache_bound;
         use_slabs = slabs;
         trace = getenv("NTL_POOL_TRACE") != nullptr; /* diagnostics: every hipMalloc / hipFree of the block cache on stderr */
     }
 
-    /* The window stream becomes MAIN (window == main) or its own stream again, at a quiet point: everything queued has run, so every
-       cached block is free on either stream and they all move to MAIN's cache.  (Switching off, WINDOW's blocks would otherwise lie
-       stranded -- counted, never handed out; switching on, the window stage's first requests miss its own cache once.) */
-    void set_window_stream(hipStream_t window)
+    /* The window stream becomes MAIN (window == main) or its own stream again -- and the side stream goes or comes with it -- at a quiet
+       point: everything queued has run, so every cached block is free on every stream and they all move to MAIN's cache.  (Switching off,
+       WINDOW's blocks would otherwise lie stranded -- counted, never handed out; switching on, the window stage's first requests miss
+       its own cache once.) */
+    void set_window_stream(hipStream_t window, hipStream_t side = nullptr)
     {
-        st[WINDOW] = window;
-        for (auto &kv : pool[WINDOW]) pool[MAIN].insert(kv);
-        pool[WINDOW].clear();
+        st[WINDOW] = window; st[SIDE] = window != st[MAIN] ? side : nullptr;
+        for (int o = WINDOW; o < NSID; o++) {
+            for (auto &kv : pool[o]) pool[MAIN].insert(kv);
+            pool[o].clear();
+        }
         for (auto &kv : xpool) {
             pool[MAIN].insert({kv.first, kv.second.p});
             for (int o = 0; o < NSID; o++) ev_put(kv.second.ev[o]);
         }
         xpool.clear();
     }
-    int sid(int want) const { return st[WINDOW] != st[MAIN] ? want : (int)MAIN; }
+    int sid(int want) const
+    {
+        if (want == SIDE && !st[SIDE]) want = WINDOW;
+        return want == WINDOW && st[WINDOW] == st[MAIN] ? (int)MAIN : want;
+    }
 
     /* A block of at least `n` bytes for work queued on stream `sid` from now on; *true_size is what give() wants back. */
     int take(size_t n, int sid_, void **out, size_t *true_size)
@@ -106,11 +116,14 @@ struct DevPool {
         return OK;
     }
     /* A block of take() goes back into the cache; used: bit per stream id that work on the block was queued on. */
-    void give(void *p, size_t bytes, unsigned used)
+    void give(void *p, size_t bytes, unsigned used_)
     {
         if (!p) return;
-        const bool on_main = used & (1u << MAIN), on_w = used & (1u << WINDOW);
-        if (on_main != on_w) pool[on_w ? WINDOW : MAIN].insert({bytes, p}); /* one stream: its own cache */
+        unsigned used = 0, n_used = 0; /* as the streams stand now (a block may outlive a switch of set_window_stream) */
+        int only = MAIN;
+        for (int o = 0; o < NSID; o++)
+            if ((used_ & (1u << o)) && !(used & (1u << sid(o)))) { used |= 1u << sid(o); n_used++; only = sid(o); }
+        if (n_used == 1) pool[only].insert({bytes, p}); /* one stream: its own cache */
         else {
             XBlock x;
             x.p = p;
@@ -133,7 +146,7 @@ struct DevPool {
             if (big && (xpool.empty() || std::prev(big->end())->first >= std::prev(xpool.end())->first)) {
                 auto it = std::prev(big->end());
                 if (trace) fprintf(stderr, "ntl pool: over the bound, hipFree %.1f MB\n", it->first / 1e6);
-                /* safe whatever is still queued: a slab block waits in limbo for both streams, a single block's hipFree for the device */
+                /* safe whatever is still queued: a slab block waits in limbo for every stream, a single block's hipFree for the device */
                 free_uncached(it->second, it->first);
                 pool_bytes -= it->first;
                 big->erase(it);
@@ -155,7 +168,7 @@ struct DevPool {
         return hipMalloc(out, bytes) == hipSuccess ? OK : NOMEM;
     }
     /* Gives a block of alloc_uncached (of `bytes`, as asked for there) back.  A single block: hipFree, which waits for the device.  A slab
-       block is not waited for: an event is recorded behind each of the two streams and the block goes into limbo; it joins the slabs'
+       block is not waited for: an event is recorded behind each of the streams and the block goes into limbo; it joins the slabs'
        free list when the events have passed (limbo_poll).
        THE ONE METHOD THAT A THREAD OTHER THAN THE POOL'S OWNER MAY CALL: it makes its own events (ev_free is the owner's) and touches only
        what slab_mu guards -- slabs, slab_free, slab_size, slab_limbo (slab_cur / slab_end are not guarded: the owner alone reads and moves
@@ -174,7 +187,7 @@ struct DevPool {
         }
         if (!L.p) { (void)hipFree(p); return; }
         /* what is still queued on the block: an event behind each of the streams; no event to be had: the slow, safe way */
-        hipStream_t s[NSID] = {st[MAIN], st[WINDOW] != st[MAIN] ? st[WINDOW] : nullptr};
+        hipStream_t s[NSID] = {st[MAIN], st[WINDOW] != st[MAIN] ? st[WINDOW] : nullptr, st[SIDE]};
         bool ok = true;
         for (int i = 0; i < NSID && ok; i++)
             if (s[i]) ok = hipEventCreateWithFlags(&L.ev[i], hipEventDisableTiming) == hipSuccess && hipEventRecord(L.ev[i], s[i]) == hipSuccess;
@@ -228,7 +241,7 @@ struct DevPool {
     }
 
 private:
-    /* a cached block that was used on both streams: whoever takes it waits for the events of the streams it is not on (nullptr: not used there) */
+    /* a cached block that was used on several streams: whoever takes it waits for the events of the streams it is not on (nullptr: not used there) */
     struct XBlock { void *p = nullptr; hipEvent_t ev[NSID] = {}; };
     struct Slab { char *base; size_t size; size_t live; };
     struct Limbo { void *p; size_t bytes; hipEvent_t ev[NSID]; }; /* a slab block that was given back while work on it may still be queued */

@@ -62,9 +62,14 @@
  * result handles are completed lazily (sketch_finalize / mapres_finalize) when a count or a record is asked for.
  * A third stream for a sketch's preparation (the per-sequence tables, the strip scan, the strip table) was measured twice and
  * removed: the step got longer (profiles/HISTORY.md, profiles/r04_prep_stream.jsonl); those kernels run on the window stream.
+ * The SIDE stream (NTL_SIDE_STREAM=1, with the pipeline on; not the default: DESIGN.md 4.6 has the measurement) takes what follows a sketch's first window kernel -- the
+ * block-minima pass over the strips it gave up and the exact passes: about one strip in a hundred, needed only by the emit kernel of
+ * the same sketch on MAIN -- so that the window kernels of consecutive sketches follow each other on the window stream with nothing
+ * but the next sketch's preparation between them.  NTL_SIDE_STREAM=2 queues that preparation on the side stream too
+ * (A/B: the side stream is one queue, so it then stands behind the previous sketch's passes).
  */
-enum { SID_MAIN = 0, SID_W = 1, NTL_NSID = 2 };
-static_assert(SID_MAIN == DevPool::MAIN && SID_W == DevPool::WINDOW && NTL_NSID == DevPool::NSID, "the pool's stream ids are the context's");
+enum { SID_MAIN = 0, SID_W = 1, SID_S = 2, NTL_NSID = 3 };
+static_assert(SID_MAIN == DevPool::MAIN && SID_W == DevPool::WINDOW && SID_S == DevPool::SIDE && NTL_NSID == DevPool::NSID, "the pool's stream ids are the context's");
 static_assert(NTL_OK == DevPool::OK && NTL_ENOMEM == DevPool::NOMEM, "the pool's return codes are the C ABI's");
 
 struct ProfEntry {
@@ -85,6 +90,9 @@ struct ntl_ctx {
     hipStream_t stream = nullptr;  /* MAIN */
     hipStream_t wstream = nullptr; /* window stage; == stream when the pipeline is off */
     hipStream_t wstream_own = nullptr; /* the second stream itself (ntl_ctx_set_pipeline switches wstream between it and MAIN) */
+    hipStream_t sstream = nullptr; /* side stream of the window stage's give-up passes; NULL while the pipeline is off, or without one */
+    hipStream_t sstream_own = nullptr;
+    bool side_prep = false;        /* NTL_SIDE_STREAM=2: a sketch's preparation on the side stream as well */
     bool pipelined = false;
     std::string err;
     std::string devname;
@@ -105,8 +113,8 @@ struct ntl_ctx {
     PendingQueue pq;                    /* the slots, the ordering events and the handles destroyed before their work had run (pending.h) */
     hipEvent_t throttle[8] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     uint64_t n_enqueued = 0;            /* sketches queued so far: the host runs at most 8 of them ahead of the device */
-    hipStream_t s(int sid) const { return sid == SID_W ? wstream : stream; }
-    int sid(int want) const { return pipelined ? want : SID_MAIN; }
+    hipStream_t s(int sid) const { return sid == SID_S ? sstream : (sid == SID_W ? wstream : stream); }
+    int sid(int want) const { return !pipelined ? SID_MAIN : (want == SID_S && !sstream ? SID_W : want); }
 };
 #define NTL_NSLOTS 512u
 
@@ -293,6 +301,20 @@ extern "C" int ntl_ctx_create(int device, ntl_ctx **out)
         if (e2 != hipSuccess) { c->wstream = c->stream; c->pipelined = false; }
         else c->wstream_own = c->wstream;
     }
+    /* NTL_SIDE_STREAM: 1 the give-up passes of a sketch on a third stream, 2 its preparation too, 0 (default) everything on the
+       window stream.  Off by default: measured on C3 the step is 0.3 ms shorter with it, inside the run-to-run spread */
+    int side = 0;
+    if (const char *e = getenv("NTL_SIDE_STREAM")) side = atoi(e);
+    if (c->pipelined && side > 0) {
+        /* its kernels are short and MAIN's emit kernel waits for them: MAIN's priority (NTL_SIDE_PRIO=0: the window stream's, A/B) */
+        bool as_main = true;
+        if (const char *e = getenv("NTL_SIDE_PRIO")) as_main = atoi(e) != 0;
+        hipError_t e3 = prio ? hipStreamCreateWithPriority(&c->sstream, hipStreamNonBlocking, (prio == 2) != as_main ? greatest : least)
+                             : hipStreamCreateWithFlags(&c->sstream, hipStreamNonBlocking);
+        if (e3 != hipSuccess) { c->sstream = nullptr; (void)hipGetLastError(); }
+        c->sstream_own = c->sstream;
+        c->side_prep = side == 2;
+    }
     {
         uint64_t g4[256][2];
         make_g4(g4);
@@ -343,7 +365,7 @@ extern "C" int ntl_ctx_create(int device, ntl_ctx **out)
         const char *se = getenv("NTL_SLABS");
         const bool slabs = !se || atoi(se) != 0;
 #endif
-        c->mem.setup(c->stream, c->wstream, cache_bound, slabs);
+        c->mem.setup(c->stream, c->wstream, cache_bound, slabs, c->sstream);
         char buf[256];
         snprintf(buf, sizeof buf, "%s %s %d CUs %.0f GiB", prop.name, prop.gcnArchName, prop.multiProcessorCount,
                  (double)prop.totalGlobalMem / (1024.0 * 1024.0 * 1024.0));
@@ -359,6 +381,7 @@ static hipError_t sync_both(ntl_ctx *c)
 {
     hipError_t e = hipStreamSynchronize(c->stream);
     if (c->wstream != c->stream) { const hipError_t e2 = hipStreamSynchronize(c->wstream); if (e == hipSuccess) e = e2; }
+    if (c->sstream) { const hipError_t e3 = hipStreamSynchronize(c->sstream); if (e == hipSuccess) e = e3; }
     return e;
 }
 
@@ -381,6 +404,7 @@ extern "C" void ntl_ctx_destroy(ntl_ctx *c)
     for (auto e : c->ev_free) (void)hipEventDestroy(e);
     for (auto &e : c->throttle) c->pq.event_put(e);
     c->pq.destroy();
+    if (c->sstream_own) (void)hipStreamDestroy(c->sstream_own);
     if (c->wstream_own) (void)hipStreamDestroy(c->wstream_own);
     (void)hipStreamDestroy(c->stream);
     delete c;
@@ -401,9 +425,13 @@ extern "C" int ntl_ctx_set_pipeline(ntl_ctx *c, int on)
     if (on && !c->wstream_own) return fail(c, NTL_EINVAL, "this context was created without a window stream (NTL_PIPELINE=0)");
     c->pipelined = on != 0;
     c->wstream = on ? c->wstream_own : c->stream;
-    c->mem.set_window_stream(c->wstream); /* (both streams were drained above: every cached block moves to MAIN's cache) */
+    c->sstream = on ? c->sstream_own : nullptr;
+    c->mem.set_window_stream(c->wstream, c->sstream); /* (the streams were drained above: every cached block moves to MAIN's cache) */
     return NTL_OK;
 }
+
+/* 1 while the window stage's give-up passes are queued on the side stream (the pipeline is on and NTL_SIDE_STREAM was 1 or 2) */
+extern "C" int ntl_ctx_side_stream(const ntl_ctx *c) { return c && c->pipelined && c->sstream ? 1 : 0; }
 
 extern "C" int ntl_ctx_sync(ntl_ctx *c)
 {
@@ -519,7 +547,10 @@ static void batch_on_wstream(ntl_ctx *c, const ntl_batch *b)
 {
     if (!c->pipelined) return;
     if (b->ready && !b->w_waited) { (void)hipStreamWaitEvent(c->wstream, b->ready, 0); b->w_waited = true; }
-    b->packed.touch(SID_W); b->seq_base.touch(SID_W); b->seq_run_first.touch(SID_W); b->run_start.touch(SID_W); b->run_len.touch(SID_W);
+    /* (the side stream's passes read it too, behind the window kernel -- so behind this wait; its preparation: sketch_prepare) */
+    for (int sid : {(int)SID_W, (int)SID_S}) {
+        b->packed.touch(sid); b->seq_base.touch(sid); b->seq_run_first.touch(sid); b->run_start.touch(sid); b->run_len.touch(sid);
+    }
 }
 
 /* a batch of nseq sequences and `bases` bases whose packed stream spans `span` positions behind the lead pad */
@@ -1339,22 +1370,22 @@ static void with_constant(int value, F &&f)
 
 /* exact 64-bit pass: over all strips (multi-run strips when `multi`), or -- redo != NULL -- over the strips the fast pass flagged */
 template <int C, int NT, int R0>
-static void launch_mask_r0(ntl_ctx *c, const SketchArgs &A, unsigned strips, bool single, bool multi)
+static void launch_mask_r0(hipStream_t st, const SketchArgs &A, unsigned strips, bool single, bool multi)
 {
     const unsigned grid = A.redo_list ? 2048u : ((strips + 7u) & ~7u);
-    if (single) hipLaunchKernelGGL((sketch_mask_kernel<C, NT, false, R0>), dim3(grid), dim3(NT), 0, c->wstream, A);
-    if (multi) hipLaunchKernelGGL((sketch_mask_kernel<C, NT, true, R0>), dim3((strips + 7u) & ~7u), dim3(NT), 0, c->wstream, A);
+    if (single) hipLaunchKernelGGL((sketch_mask_kernel<C, NT, false, R0>), dim3(grid), dim3(NT), 0, st, A);
+    if (multi) hipLaunchKernelGGL((sketch_mask_kernel<C, NT, true, R0>), dim3((strips + 7u) & ~7u), dim3(NT), 0, st, A);
 }
 
 template <int C>
-static void launch_mask(ntl_ctx *c, const SketchArgs &A, unsigned strips, bool single, bool multi, int nt)
+static void launch_mask(hipStream_t st, const SketchArgs &A, unsigned strips, bool single, bool multi, int nt)
 {
     /* 16 k-mers per lane: one instantiation per strip width, R0 at run time (this is the redo / multi-run pass since the 32-bit
        window pass took over the common case); 4 and 1 k-mers per lane (w < 16): R0 as a template parameter */
-    if (C == 16 && nt == 128) launch_mask_r0<C, 128, -1>(c, A, strips, single, multi);
-    else if (C == 16 && nt == SK_NT_LONG) { if constexpr (C == 16) launch_mask_r0<16, SK_NT_LONG, -1>(c, A, strips, single, multi); }
-    else if (C == 16) launch_mask_r0<C, SK_NT, -1>(c, A, strips, single, multi);
-    else with_constant<0, C>(A.G.r0, [&](auto r0) { launch_mask_r0<C, SK_NT, decltype(r0)::value>(c, A, strips, single, multi); });
+    if (C == 16 && nt == 128) launch_mask_r0<C, 128, -1>(st, A, strips, single, multi);
+    else if (C == 16 && nt == SK_NT_LONG) { if constexpr (C == 16) launch_mask_r0<16, SK_NT_LONG, -1>(st, A, strips, single, multi); }
+    else if (C == 16) launch_mask_r0<C, SK_NT, -1>(st, A, strips, single, multi);
+    else with_constant<0, C>(A.G.r0, [&](auto r0) { launch_mask_r0<C, SK_NT, decltype(r0)::value>(st, A, strips, single, multi); });
 }
 
 /* workgroups of `threads` lanes of a kernel that one CU holds at once */
@@ -1604,8 +1635,9 @@ static int window_plan(ntl_ctx *c, const ntl_batch *b, int k, int w, bool no_lis
     return NTL_OK;
 }
 
-/* the 32-bit pass of the plan over the single-run strips (sketch2_kernels.h), on the window stream */
-static void launch_window_pass(ntl_ctx *c, const WindowPlan &P, const Sketch2Args &B)
+/* the 32-bit pass of the plan over the single-run strips (sketch2_kernels.h), on the window stream; true: it leaves a list of strips
+   it gave up, for launch_give_up_pass */
+static bool launch_window_pass(ntl_ctx *c, const WindowPlan &P, const Sketch2Args &B)
 {
     const unsigned strips = B.A.nstrips;
     const dim3 grid((strips + 7u) & ~7u);
@@ -1618,7 +1650,7 @@ static void launch_window_pass(ntl_ctx *c, const WindowPlan &P, const Sketch2Arg
             else if (P.big) hipLaunchKernelGGL((sketch_fast_kernel<SK_NT, R0, true>), grid, dim3(SK_NT), 0, c->wstream, B);
             else hipLaunchKernelGGL((sketch_fast_kernel<SK_NT, R0, false>), grid, dim3(SK_NT), 0, c->wstream, B);
         });
-        return;
+        return false;
     case WP_THRESH:
         if (P.direct) hipLaunchKernelGGL((sketch_thresh_kernel<256, true>), grid, dim3(256), 0, c->wstream, B);
         else hipLaunchKernelGGL((sketch_thresh_kernel<256, false>), grid, dim3(256), 0, c->wstream, B);
@@ -1647,23 +1679,37 @@ static void launch_window_pass(ntl_ctx *c, const WindowPlan &P, const Sketch2Arg
             hipLaunchKernelGGL(kern, dim3(wgs), dim3(threads), 0, c->wstream, Bq);
         });
         break;
-    default: return;
+    default: return false;
     }
-    /* what the threshold and wave kernels gave up (a window without a candidate: 0.7 % of the strips): the block-minima pass over that list */
+    return true;
+}
+
+/* what the threshold and wave kernels gave up (a window without a candidate: 0.7 % of the strips): the block-minima pass over that list,
+   on stream st behind them */
+static void launch_give_up_pass(hipStream_t st, const WindowPlan &P, const Sketch2Args &B)
+{
+    const unsigned strips = B.A.nstrips;
     with_constant<0, 16>(P.G.r0, [&](auto r0) {
         constexpr int R0 = decltype(r0)::value;
         const dim3 lgrid(std::min(strips, 4096u));
-        if (P.nt == SK_NT_LONG && P.big) hipLaunchKernelGGL((sketch_fast_list_kernel<SK_NT_LONG, R0, true>), lgrid, dim3(SK_NT_LONG), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
-        else if (P.nt == SK_NT_LONG) hipLaunchKernelGGL((sketch_fast_list_kernel<SK_NT_LONG, R0>), lgrid, dim3(SK_NT_LONG), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
-        else if (P.big) hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0, true>), lgrid, dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
-        else hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0>), lgrid, dim3(256), 0, c->wstream, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        if (P.nt == SK_NT_LONG && P.big) hipLaunchKernelGGL((sketch_fast_list_kernel<SK_NT_LONG, R0, true>), lgrid, dim3(SK_NT_LONG), 0, st, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        else if (P.nt == SK_NT_LONG) hipLaunchKernelGGL((sketch_fast_list_kernel<SK_NT_LONG, R0>), lgrid, dim3(SK_NT_LONG), 0, st, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        else if (P.big) hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0, true>), lgrid, dim3(256), 0, st, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
+        else hipLaunchKernelGGL((sketch_fast_list_kernel<256, R0>), lgrid, dim3(256), 0, st, B, (const uint32_t *)B.fb_list, (const uint32_t *)B.fb_count);
     });
 }
 
 /* What one sketch_enqueue holds between its stages.  The temporaries return to the context's cache when it ends: every later user of
- * those blocks is queued behind the kernels of this sketch on the stream they were used on, so no wait is needed. */
+ * those blocks is queued behind the kernels of this sketch on the stream they were used on, so no wait is needed -- and a block that
+ * several streams used goes back with an event behind each (DevBuf::touch), so that the next sketch, whose window kernel runs beside
+ * this one's give-up passes, gets it only once they have run, and another block until then. */
 struct SketchWork {
     int wsid; hipStream_t ws, ms; /* the window stage's stream id (MAIN when the pipeline is off), its stream, MAIN */
+    int ssid; hipStream_t ss;     /* the stream of the passes behind the first window kernel: the side stream, or the window stage's */
+    int psid; hipStream_t ps;     /* the preparation's stream: the window stage's (NTL_SIDE_STREAM=2: the side stream) */
+    hipStream_t last;             /* where the window stage's last kernel was queued: the emit stage on MAIN waits for it */
+    /* queued on `on`; stream `then` goes on behind it */
+    static int order(ntl_ctx *c, hipStream_t on, hipStream_t then);
     uint64_t nmask; /* words of the bitmask: one bit per base */
     DevBuf run_n, run_ord, seq_M, nstrips, strip_first, tile, redo, strip_tab; /* (nstrips / strip_first: nseq+1 entries, the scan leaves the total behind the last) */
     SeqTables T; StripLists Ls = {}; StripZero Z = {};
@@ -1676,19 +1722,35 @@ struct SketchWork {
 };
 static const uint64_t REDO_HEAD = 16 + 8 * 16; /* words in front of the two lists of `redo` */
 
-/* Preparation, on the window stream in front of the window kernels: the temporaries, the batch's tables, the strips' tables */
+int SketchWork::order(ntl_ctx *c, hipStream_t on, hipStream_t then)
+{
+    if (on == then) return NTL_OK;
+    hipEvent_t e = c->pq.event_get();
+    if (!e) return fail(c, NTL_EDEVICE, "hipEventCreate failed");
+    HIPCHK(c, hipEventRecord(e, on));
+    HIPCHK(c, hipStreamWaitEvent(then, e, 0));
+    c->pq.event_put(e); /* the wait holds what it needs; the handle may be recorded again */
+    return NTL_OK;
+}
+
+/* Preparation, on the window stream in front of the window kernels: the temporaries, the batch's tables, the strips' tables.  Every
+   block is taken for the stream that writes it first (W.psid) and marked for the others that use it: the window kernel's (wsid), the
+   give-up passes' (ssid), MAIN. */
 static int sketch_prepare(ntl_ctx *c, const ntl_batch *b, int k, int w, const WindowPlan &P, ntl_sketch *s, SketchWork &W)
 {
     const uint64_t nseq = b->nseq, ub_strips = P.strips;
-    const int wsid = W.wsid;
+    const int wsid = W.wsid, psid = W.psid;
+    auto window_stage_uses = [&](const DevBuf &d) { d.touch(wsid); d.touch(W.ssid); }; /* the window kernel and the passes behind it */
     int rc;
     W.nmask = (b->total_gpos + 31) / 32 + 1;
-    if ((rc = W.run_n.alloc(c, (b->nruns + 1) * 4, wsid)) || (rc = W.run_ord.alloc(c, (b->nruns + 1) * 4, wsid)) ||
-        (rc = W.seq_M.alloc(c, (nseq + 1) * 4, wsid)) || (rc = W.nstrips.alloc(c, (nseq + 1) * 4, wsid)) ||
-        (rc = W.strip_first.alloc(c, (nseq + 2) * 4, wsid)) || (rc = s->mx_off.alloc(c, (nseq + 1) * 4)) ||
-        (rc = s->sums.alloc(c, sizeof(SketchSums), wsid))) return rc;
+    if ((rc = W.run_n.alloc(c, (b->nruns + 1) * 4, psid)) || (rc = W.run_ord.alloc(c, (b->nruns + 1) * 4, psid)) ||
+        (rc = W.seq_M.alloc(c, (nseq + 1) * 4, psid)) || (rc = W.nstrips.alloc(c, (nseq + 1) * 4, psid)) ||
+        (rc = W.strip_first.alloc(c, (nseq + 2) * 4, psid)) || (rc = s->mx_off.alloc(c, (nseq + 1) * 4)) ||
+        (rc = s->sums.alloc(c, sizeof(SketchSums), psid))) return rc;
+    window_stage_uses(W.run_n); window_stage_uses(W.run_ord); window_stage_uses(W.seq_M);
     s->sums.touch(SID_MAIN); /* zeroed by strip_table_kernel on the window stream, added to and read on MAIN */
     batch_on_wstream(c, b);
+    if (W.ps != W.ws && b->ready) HIPCHK(c, hipStreamWaitEvent(W.ps, b->ready, 0));
     SeqTables &T = W.T;
     T.packed = b->packed.as<uint32_t>(); T.seq_base = b->seq_base.as<uint64_t>();
     T.seq_run_first = b->seq_run_first.as<uint32_t>(); T.run_start = b->run_start.as<uint32_t>();
@@ -1697,7 +1759,8 @@ static int sketch_prepare(ntl_ctx *c, const ntl_batch *b, int k, int w, const Wi
     if (P.lists) {
         Ls.slot = P.slot; Ls.ovf_base = (uint32_t)((ub_strips + 1) * P.slot); Ls.ovf_cap = P.pool;
         /* cnt[ub_strips + 1] (+ the two control words behind it), zeroed: a strip nobody lists has none */
-        if ((rc = W.lcnt.alloc(c, (ub_strips + 4) * 4, wsid)) || (rc = W.lent.alloc(c, ((ub_strips + 1) * P.slot + P.pool) * 4, wsid)) || (rc = W.loff.alloc(c, (ub_strips + 2) * 4))) return rc;
+        if ((rc = W.lcnt.alloc(c, (ub_strips + 4) * 4, psid)) || (rc = W.lent.alloc(c, ((ub_strips + 1) * P.slot + P.pool) * 4, wsid)) || (rc = W.loff.alloc(c, (ub_strips + 2) * 4))) return rc;
+        window_stage_uses(W.lcnt); window_stage_uses(W.lent); /* the lists, their pool and its fail flag (Ls.ctl): this sketch's alone until the emit kernel has read them */
         W.lcnt.touch(SID_MAIN); W.lent.touch(SID_MAIN);
         Ls.cnt = W.lcnt.as<uint32_t>(); Ls.ent = W.lent.as<uint32_t>(); Ls.ctl = Ls.cnt + ub_strips + 2;
     }
@@ -1706,27 +1769,29 @@ static int sketch_prepare(ntl_ctx *c, const ntl_batch *b, int k, int w, const Wi
        strips' counts -- by strip_table_kernel: one launch instead of three fills on the window stream's critical path (round 5) */
     StripZero &Z = W.Z;
     if (P.fast() && ub_strips) {
-        if ((rc = W.redo.alloc(c, (REDO_HEAD + 2 * ub_strips + 4) * 4, wsid))) return rc;
+        if ((rc = W.redo.alloc(c, (REDO_HEAD + 2 * ub_strips + 4) * 4, psid))) return rc;
+        window_stage_uses(W.redo);
         Z.head = W.redo.as<uint32_t>(); Z.nhead = (uint32_t)REDO_HEAD;
         Z.cnt = Ls.cnt; Z.ncnt = Ls.cnt ? (uint32_t)(ub_strips + 4) : 0u;
     }
     W.mask.c = c;
     if (!P.lists && (rc = mask_take(c, W.nmask * 4, wsid, &W.mask))) return rc;
-    if ((rc = W.strip_tab.alloc(c, (ub_strips + 1) * sizeof(StripInfo), wsid)) || (rc = W.strip_lite.alloc(c, (ub_strips + 1) * sizeof(StripLite), wsid))) return rc;
+    if ((rc = W.strip_tab.alloc(c, (ub_strips + 1) * sizeof(StripInfo), psid)) || (rc = W.strip_lite.alloc(c, (ub_strips + 1) * sizeof(StripLite), psid))) return rc;
+    window_stage_uses(W.strip_tab); window_stage_uses(W.strip_lite);
     SketchSums *dsums = s->sums.as<SketchSums>();
     /* the device sums are zeroed by strip_table_kernel (StripZero), in front of the window kernels on their stream; every kernel that
        writes them runs on MAIN behind the window stage (sketch_enqueue's event; one stream when the pipeline is off).  No sequence, no kernel: a fill */
     Z.sums = (uint32_t *)dsums; Z.nsums = (uint32_t)(sizeof(SketchSums) / 4);
     if (!nseq) HIPCHK(c, hipMemsetAsync(dsums, 0, sizeof(SketchSums), W.ms));
-    ProfSpan sp(c, "sketch_meta", wsid);
+    ProfSpan sp(c, "sketch_meta", psid);
     if (nseq) {
         KTables K;
         K.run_n = W.run_n.as<uint32_t>(); K.run_ord = W.run_ord.as<uint32_t>();
         K.seq_M = W.seq_M.as<uint32_t>(); K.seq_nstrips = W.nstrips.as<uint32_t>();
-        hipLaunchKernelGGL(seq_meta_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, W.ws, T, K, k, w, P.G.NWO);
+        hipLaunchKernelGGL(seq_meta_kernel, dim3((unsigned)((nseq + 255) / 256)), dim3(256), 0, W.ps, T, K, k, w, P.G.NWO);
         HIPCHK(c, hipGetLastError());
-        if ((rc = device_scan(c, W.nstrips.as<uint32_t>(), W.strip_first.as<uint32_t>(), nseq, nullptr, 1, nullptr, wsid))) return rc;
-        hipLaunchKernelGGL(strip_table_kernel, dim3((unsigned)((ub_strips + 255) / 256 + 1)), dim3(256), 0, W.ws, T, (const uint32_t *)K.run_n,
+        if ((rc = device_scan(c, W.nstrips.as<uint32_t>(), W.strip_first.as<uint32_t>(), nseq, nullptr, 1, nullptr, psid))) return rc;
+        hipLaunchKernelGGL(strip_table_kernel, dim3((unsigned)((ub_strips + 255) / 256 + 1)), dim3(256), 0, W.ps, T, (const uint32_t *)K.run_n,
                            (const uint32_t *)K.run_ord, (const uint32_t *)K.seq_M, (const uint32_t *)W.strip_first.as<uint32_t>(), P.G.NWO,
                            P.C * P.nt, W.strip_tab.as<StripInfo>(), (uint32_t)ub_strips + 1u, W.strip_lite.as<StripLite>(), Z);
         HIPCHK(c, hipGetLastError());
@@ -1755,10 +1820,15 @@ static int g8k_for(ntl_ctx *c, int k, hipStream_t ws, uint32_t rev_a, uint32_t r
     return NTL_OK;
 }
 
-/* The window stage: the plan's 32-bit pass, the exact pass over what it flagged (redo) and over the multi-run strips; or the exact pass alone */
+/* The window stage: the plan's 32-bit pass, the exact pass over what it flagged (redo) and over the multi-run strips; or the exact pass alone.
+   The 32-bit pass's first kernel runs on the window stream; what follows it (W.ss: the side stream, where there is one) reads and writes
+   only this sketch's blocks and the slot, and is needed by nothing but this sketch's emit stage, which waits for W.last. */
 static int sketch_window_stage(ntl_ctx *c, const ntl_batch *b, int k, const WindowPlan &P, ntl_sketch *s, SketchWork &W)
 {
     const uint64_t ub_strips = P.strips;
+    int rc;
+    W.last = W.ws;
+    if ((rc = SketchWork::order(c, W.ps, W.ws))) return rc; /* preparation -> window kernels */
     if (!ub_strips) return NTL_OK;
     const int wsid = W.wsid, nt = P.nt;
     SketchArgs A = {}; /* (redo_list, redo_count, redo_out: null) */
@@ -1771,9 +1841,9 @@ static int sketch_window_stage(ntl_ctx *c, const ntl_batch *b, int k, const Wind
     if (!P.fast()) {
         ProfSpan sp(c, "sketch_mask", wsid);
         if (P.pass == WP_SMALL) launch_small(c, A, (unsigned)ub_strips, b->any_multi);
-        else if (P.C == 16) launch_mask<16>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
-        else if (P.C == 4) launch_mask<4>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
-        else launch_mask<1>(c, A, (unsigned)ub_strips, true, b->any_multi, nt);
+        else if (P.C == 16) launch_mask<16>(W.ws, A, (unsigned)ub_strips, true, b->any_multi, nt);
+        else if (P.C == 4) launch_mask<4>(W.ws, A, (unsigned)ub_strips, true, b->any_multi, nt);
+        else launch_mask<1>(W.ws, A, (unsigned)ub_strips, true, b->any_multi, nt);
         HIPCHK(c, hipGetLastError());
         return NTL_OK;
     }
@@ -1785,21 +1855,29 @@ static int sketch_window_stage(ntl_ctx *c, const ntl_batch *b, int k, const Wind
     B.redo_list = redo + REDO_HEAD; B.fb_list = B.redo_list + ub_strips + 2;
     B.max_word = b->nwords_packed - 1;
     B.q16 = k / 16; B.r16 = k % 16; B.rev_a = (uint32_t)(k - 1) % 33u; B.rev_b = (uint32_t)(k - 1) % 31u;
-    if (int rc = g8k_for(c, k, W.ws, B.rev_a, B.rev_b, &B.g8k)) return rc;
+    if ((rc = g8k_for(c, k, W.ws, B.rev_a, B.rev_b, &B.g8k))) return rc;
     B.g4k = B.g8k + 2 * 65536;
+    bool gave_up;
     {
         ProfSpan sp(c, "sketch_mask", wsid);
-        launch_window_pass(c, P, B);
+        gave_up = launch_window_pass(c, P, B);
         HIPCHK(c, hipGetLastError());
     }
-    ProfSpan sp(c, "sketch_redo", wsid);
+    if ((rc = SketchWork::order(c, W.ws, W.ss))) return rc; /* first window kernel -> the passes over what it left */
+    W.last = W.ss;
+    if (gave_up) {
+        ProfSpan sp(c, "sketch_mask", W.ssid);
+        launch_give_up_pass(W.ss, P, B);
+        HIPCHK(c, hipGetLastError());
+    }
+    ProfSpan sp(c, "sketch_redo", W.ssid);
     SketchArgs R = A;
     R.redo_count = B.redo_count; R.redo_list = B.redo_list;
-    /* the redo pass writes the two counts into the slot (`redo` never leaves the window stream); s->lz.done, on MAIN behind the
-       emit kernel, is behind it too (window stage -> emit) */
+    /* the redo pass writes the two counts into the slot (`redo` never leaves the window stage's streams); s->lz.done, on MAIN behind
+       the emit kernel, is behind it too (window stage's last kernel -> emit) */
     R.redo_out = &((SketchSums *)c->pq.slot_dev(s->lz.slot))->redo_n;
-    launch_mask<16>(c, R, (unsigned)ub_strips, true, false, nt);
-    if (b->any_multi) launch_mask<16>(c, A, (unsigned)ub_strips, false, true, nt);
+    launch_mask<16>(W.ss, R, (unsigned)ub_strips, true, false, nt);
+    if (b->any_multi) launch_mask<16>(W.ss, A, (unsigned)ub_strips, false, true, nt);
     HIPCHK(c, hipGetLastError());
     return NTL_OK;
 }
@@ -1940,16 +2018,14 @@ static int sketch_enqueue(ntl_ctx *c, const ntl_batch *b, int k, int w, const nt
     if ((rc = window_plan(c, b, k, w, s->no_lists, P))) return rc;
     SketchWork W;
     W.wsid = c->sid(SID_W); W.ws = c->s(W.wsid); W.ms = c->stream;
+    W.ssid = c->sid(SID_S); W.ss = c->s(W.ssid);
+    W.psid = c->side_prep ? W.ssid : W.wsid; W.ps = c->s(W.psid);
     if ((rc = sketch_prepare(c, b, k, w, P, s, W))) return rc;
     if ((rc = sketch_window_stage(c, b, k, P, s, W))) return rc;
-    if (W.ws != W.ms) { /* window stage -> emit */
-        hipEvent_t e = c->pq.event_get();
-        if (!e) return fail(c, NTL_EDEVICE, "hipEventCreate failed");
-        HIPCHK(c, hipEventRecord(e, W.ws));
-        HIPCHK(c, hipStreamWaitEvent(W.ms, e, 0));
-        c->pq.event_put(e); /* the wait holds what it needs; the handle may be recorded again */
-    }
+    if ((rc = SketchWork::order(c, W.last, W.ms))) return rc; /* window stage -> emit */
     if ((rc = sketch_emit_stage(c, b, k, P, ix, s, cap, W))) return rc;
+    /* "lists complete" reaches the handle and the throttle through MAIN: both events are recorded behind the emit kernel, which waited for
+       the side stream's last pass -- the host never runs further ahead of the give-up passes than of the emit kernels */
     HIPCHK(c, hipEventRecord(s->lz.done, W.ms));
     if (!throttle) throttle = c->pq.event_get();
     if (throttle) HIPCHK(c, hipEventRecord(throttle, W.ms));
