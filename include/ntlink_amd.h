@@ -16,6 +16,8 @@
  *                 duplicate filter of the k15 w5 sketch
  *   ntl_overlap_cuts  shared minimizers, their runs   <- merge_overlapping (bin/ntlink_overlap_sequences.py:341-417) with
  *                 and the cut of every adjacent pair     filter_minimizers_position (:304-322), get_dist_from_end (:335-339)
+ *   ntl_path_chains  linearize, transitive filter and   <- linearize_graph .. remove_duplicate_paths
+ *                 the chains of the path graph            (bin/ntlink_stitch_paths.py:221-365)
  *   ntl_index_*   contig minimizer index            <- NtLink.read_minimizers
  *                                                      (bin/ntlink_pair.py:189-211)
  *   ntl_map_*     per-read lookup, hit filtering,   <- NtLink.find_scaffold_pairs body
@@ -368,6 +370,46 @@ int ntl_overlap_filter(ntl_ctx *ctx, const ntl_sketch *s, const uint64_t *region
 typedef struct { uint32_t src, tgt, src_start, src_end, tgt_start, tgt_end, src_len, tgt_len, signs, pad; } ntl_overlap_pair;
 typedef struct { uint32_t status, n_shared, n_comp, src_cut, tgt_cut, pad; uint64_t hash; } ntl_overlap_cut;
 int ntl_overlap_cuts(ntl_ctx *ctx, const ntl_sketch *s, const ntl_overlap_pair *pairs, uint64_t n_pairs, ntl_overlap_cut *out);
+
+/* ---- path chains ----------------------------------------------------------------------- */
+
+/* The graph half of the stitch-paths stage: linearize_graph (bin/ntlink_stitch_paths.py:221-254), is_graph_linear (:256-265),
+ * transitive_filter / has_transitive_support (:327-365), find_paths / find_paths_process (:282-300, :314-325) and
+ * remove_duplicate_paths (:302-312), on the device (csrc/path_kernels.h).  The reference builds an igraph graph, copies it per
+ * filter and takes a subgraph and a shortest path per component.  The call waits once.
+ *
+ * Vertices are oriented contigs, 2 * contig + (orientation == '-'), so n_vertices is even and the twin of v is v ^ 1.
+ *   edges[n_edges]   {src, tgt, d, n, flags}: d the gap, n how many path files gave the edge, NTL_PATH_EDGE_NEW in flags where
+ *                    path_id is "new".  Every edge stands beside its twin (tgt ^ 1, src ^ 1) with the same d, n and flags,
+ *                    and no (src, tgt) occurs twice.
+ *   links[n_links]   {a, b}: the directed edges of the scaffold graph, read in mode NTL_PATH_TRANSITIVE only
+ *   mode             NTL_PATH_CONSERVATIVE: the graph as it is (--conservative); NTL_PATH_STITCH: linearize_graph first;
+ *                    NTL_PATH_TRANSITIVE: then transitive_filter (--transitive)
+ * Out, caller-owned:
+ *   chain_off[n_vertices / 2 + 1]  chain i is chain_vertex[chain_off[i] .. chain_off[i + 1]), head to tail; chain_off[n_chains]
+ *                                  is counts->n_chain_vertices
+ *   chain_vertex[n_vertices]       chains of two or more vertices, in the order of their heads' numbers; of a chain and its twin
+ *                                  (reversed, every vertex ^ 1) the one with head <= (tail ^ 1); a chain that is its own twin once
+ *   chain_d[n_vertices]            beside every vertex the d of the edge behind it, 0 beside a chain's last
+ *   counts                         the two totals, the edges removed by linearize_graph and by transitive_filter, and the
+ *                                  components that are cycles (find_paths_process finds no source there: they give no path)
+ * Linearize, per vertex and side (:224-249): at a vertex with two or more in-edges (out-edges) one edge stays only if ALL of them
+ * are new and the largest n is unique -- every other new edge there goes, edges that are not new always stay; an edge goes if
+ * either end says so.  Transitive support of a new edge (s, t) comes from scaffold-graph edges (a, b) with a == s or before it and
+ * b == t or behind it on the chain: a != s and b != t is full support, a == s alone source, b == t alone target support, and the
+ * edge stays iff it has full support or both of the others.
+ * NTL_EINVAL with a message: a vertex beyond n_vertices, an odd n_vertices, an edge twice or without its twin, unknown flags or
+ * mode, a graph that is not linear after linearize (the reference's assert), a NULL array with a non-zero count, 2^31 vertices. */
+#define NTL_PATH_EDGE_NEW 1u
+#define NTL_PATH_CONSERVATIVE 0u
+#define NTL_PATH_STITCH 1u
+#define NTL_PATH_TRANSITIVE 2u
+typedef struct { uint32_t src, tgt; int32_t d; uint32_t n, flags; } ntl_path_edge;
+typedef struct { uint32_t a, b; } ntl_path_link;
+typedef struct { uint32_t n_chain_vertices, n_chains, removed_linearize, removed_transitive, cycles, reserved[3]; } ntl_path_counts;
+int ntl_path_chains(ntl_ctx *ctx, uint32_t n_vertices, const ntl_path_edge *edges, uint64_t n_edges, const ntl_path_link *links,
+                    uint64_t n_links, uint32_t mode, uint32_t *chain_off, uint32_t *chain_vertex, int32_t *chain_d,
+                    ntl_path_counts *counts);
 
 /* ---- contig index ---------------------------------------------------------------------- */
 

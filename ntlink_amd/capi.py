@@ -25,7 +25,7 @@ SYMBOLS = [
     "ntl_stitched_base_counts",
     "ntl_sketch_run", "ntl_sketch_run_indexed", "ntl_sketch_run_for_map", "ntl_sketch_has_records", "ntl_sketch_destroy", "ntl_sketch_nseq", "ntl_sketch_count", "ntl_sketch_download",
     "ntl_sketch_strips", "ntl_sketch_redo_strips", "ntl_sketch_fallback_strips", "ntl_sketch_from_lists", "ntl_sketch_plan", "ntl_sketch_wait", "ntl_mapres_wait",
-    "ntl_sketch_from_host", "ntl_overlap_filter", "ntl_overlap_cuts",
+    "ntl_sketch_from_host", "ntl_overlap_filter", "ntl_overlap_cuts", "ntl_path_chains",
     "ntl_index_build", "ntl_index_destroy", "ntl_index_size",
     "ntl_map_run", "ntl_mapres_destroy", "ntl_mapres_n_mappings", "ntl_mapres_n_hits", "ntl_mapres_n_pafs",
     "ntl_mapres_n_index_hits", "ntl_mapres_download", "ntl_mapres_from_host", "ntl_mapres_liftover", "ntl_map_run_grouped", "ntl_mapres_grouped_info", "ntl_mapres_gap_cuts",
@@ -58,6 +58,11 @@ OVERLAP_PAIR_DT = np.dtype([(nm, "<u4") for nm in ("src", "tgt", "src_start", "s
                                                    "pad")])  # ntl_overlap_pair
 OVERLAP_CUT_DT = np.dtype([(nm, "<u4") for nm in ("status", "n_shared", "n_comp", "src_cut", "tgt_cut", "pad")] + [("hash", "<u8")])  # ntl_overlap_cut
 NTL_OVERLAP_CUT, NTL_OVERLAP_GLOBAL, NTL_OVERLAP_LDS_SLICE, NTL_OVERLAP_SRC_MINUS, NTL_OVERLAP_TGT_MINUS = 1, 2, 1024, 1, 2
+PATH_EDGE_DT = np.dtype([("src", "<u4"), ("tgt", "<u4"), ("d", "<i4"), ("n", "<u4"), ("flags", "<u4")])  # ntl_path_edge
+PATH_LINK_DT = np.dtype([("a", "<u4"), ("b", "<u4")])  # ntl_path_link
+PATH_COUNTS_DT = np.dtype([(nm, "<u4") for nm in ("n_chain_vertices", "n_chains", "removed_linearize", "removed_transitive", "cycles")] +
+                          [("reserved", "<u4", (3,))])  # ntl_path_counts
+NTL_PATH_EDGE_NEW, NTL_PATH_CONSERVATIVE, NTL_PATH_STITCH, NTL_PATH_TRANSITIVE = 1, 0, 1, 2
 LIFT_ENTRY_DT = np.dtype([(nm, "<u4") for nm in ("new_ctg", "mode", "scaf_start", "ctg_start", "ctg_end")])  # ntl_lift_entry
 NTL_LIFT_ABSENT, NTL_LIFT_KEEP, NTL_LIFT_SHIFT, NTL_LIFT_MIRROR = 0, 1, 2, 3  # ntl_lift_entry.mode
 NTL_LIFT_LANE_LINES = 16
@@ -176,6 +181,7 @@ def load(path=None):
     L.ntl_sketch_from_host.argtypes = [vp, C.c_uint64, u64p, u64p, u32p, u8p, C.POINTER(vp)]
     L.ntl_overlap_filter.argtypes = [vp, vp, u64p, u32p, u32p, C.POINTER(vp)]
     L.ntl_overlap_cuts.argtypes = [vp, vp, vp, C.c_uint64, vp]
+    L.ntl_path_chains.argtypes = [vp, C.c_uint32, vp, C.c_uint64, vp, C.c_uint64, C.c_uint32, vp, vp, vp, vp]
     L.ntl_index_build.argtypes = [vp, vp, u32p, C.c_uint32, C.POINTER(vp)]
     L.ntl_index_destroy.argtypes = [vp]
     L.ntl_index_destroy.restype = None
@@ -826,6 +832,28 @@ class Device:
         out = np.zeros(len(pr), OVERLAP_CUT_DT)
         self._chk(self.L.ntl_overlap_cuts(self.ptr, sketch.ptr, pr.ctypes.data if len(pr) else None, len(pr), out.ctypes.data if len(pr) else None))
         return out
+
+    def path_chains(self, n_vertices, edges, links=None, mode=NTL_PATH_STITCH):
+        """The graph half of the stitch-paths stage (ntl_path_chains, csrc/path_kernels.h): vertices 2 * contig + (ori == '-'), `edges`
+        PATH_EDGE_DT records (or tuples) src, tgt, d, n, flags -- every edge beside its twin (tgt ^ 1, src ^ 1) --, `links` the
+        scaffold graph's edges as PATH_LINK_DT (read with mode NTL_PATH_TRANSITIVE only).  -> (chain_off u32[n_chains + 1],
+        chain_vertex u32, chain_d i32, counts): the vertices of every emitted chain from head to tail, beside each the d of the edge
+        behind it (0 beside the last), and the PATH_COUNTS_DT record.  Waits for the device."""
+        ed = np.ascontiguousarray(edges if isinstance(edges, np.ndarray) else np.array(list(edges), PATH_EDGE_DT), PATH_EDGE_DT)
+        lk = np.zeros(0, PATH_LINK_DT) if links is None else \
+            np.ascontiguousarray(links if isinstance(links, np.ndarray) else np.array(list(links), PATH_LINK_DT), PATH_LINK_DT)
+        if ed.ndim != 1 or lk.ndim != 1:
+            raise ValueError("edges and links must be one-dimensional")
+        n_vertices = int(n_vertices)
+        if not 0 <= n_vertices < 1 << 31:
+            raise ValueError("n_vertices must be in 0 .. 2^31 - 1")
+        off = np.zeros(n_vertices // 2 + 1, np.uint32)
+        vertex, d = np.zeros(max(n_vertices, 1), np.uint32), np.zeros(max(n_vertices, 1), np.int32)
+        counts = np.zeros(1, PATH_COUNTS_DT)
+        self._chk(self.L.ntl_path_chains(self.ptr, n_vertices, ed.ctypes.data if len(ed) else None, len(ed), lk.ctypes.data if len(lk) else None,
+                                         len(lk), int(mode), off.ctypes.data, vertex.ctypes.data, d.ctypes.data, counts.ctypes.data))
+        n_chains, total = int(counts["n_chains"][0]), int(counts["n_chain_vertices"][0])
+        return off[:n_chains + 1].copy(), vertex[:total].copy(), d[:total].copy(), counts[0]
 
     def gap_select(self, block, ctg_len, large_k, table):
         """The candidates of one block of verbose mappings (ntl_gap_select, csrc/gap_select_kernels.h): `block` as formats.read_verbose

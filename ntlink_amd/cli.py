@@ -172,6 +172,75 @@ def overlap_sequences_main(argv=None):
     return 0
 
 
+def stitch_paths_parser():
+    p = argparse.ArgumentParser(prog="ntlink_stitch_paths.py", description="ntLink: Scaffolding genome assemblies using long reads. "
+                                                                           "This step further stitches together paths.")
+    p.add_argument("PATH", help="abyss-scaffold path files", nargs="+")
+    p.add_argument("--min_n", help="Minimum 'n' specified to abyss-scaffold", required=True, type=int)
+    p.add_argument("--max_n", help="Maximum 'n' specified to abyss-scaffold", required=True, type=int)
+    p.add_argument("-g", help="Unfiltered scaffold graph dot file", required=True, type=str)
+    p.add_argument("-a", help="Ratio of best to second best edge to create potential connection", required=False, default=0.3, type=float)
+    p.add_argument("--max_gap", help="Maximum gap between contigs. -1 for no maximum gap size [-1]", required=False, default=-1, type=int)
+    p.add_argument("-o", help="Output path file name", required=True)
+    p.add_argument("-p", help="Output file prefix", required=False, default="out", type=str)
+    p.add_argument("--transitive", help="Require transitive support for edges?", action="store_true")
+    p.add_argument("--conservative", help="Conservative mode - take optimal N50 paths, no stitching", action="store_true")
+    p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    p.add_argument("-v", "--version", action="version", version=VERSION)
+    return p
+
+
+def stitch_paths_main(argv=None):
+    """The stitch-paths stage (stitch_paths.stitch_paths) behind the reference's command line (bin/ntlink_stitch_paths.py:458-477).
+    Any error: a message, no -o file left, exit status 1."""
+    a = stitch_paths_parser().parse_args(argv)
+    from . import stitch_paths
+    try:
+        dev = _device(a.device)
+        try:
+            stitch_paths.stitch_paths(a, dev)
+        finally:
+            dev.close()
+    except Exception as exc:
+        sys.stdout.flush()
+        print(f"ERROR: {type(exc).__name__}: {exc}", file=sys.stderr)
+        return 1
+    return 0
+
+
+def filter_sequences_parser():
+    p = argparse.ArgumentParser(prog="ntlink_filter_sequences.py", description="Filter input fasta sequences based on ntLink paths")
+    p.add_argument("-s", "--fasta", help="Input fasta file", required=True, type=str)
+    p.add_argument("-d", "--dot", help="Input scaffold graph dot file", required=True, type=str)
+    p.add_argument("-a", "--path", help="Input path file", required=True, type=str)
+    p.add_argument("-k", help="K-mer size (bp)", required=True, type=int)
+    p.add_argument("-f", help="Fudge factor for estimated overlap [0.5]", type=float, default=0.5)
+    p.add_argument("-g", help="Minimum gap size (bp) [20]", required=False, type=int, default=20)
+    p.add_argument("-t", help="Number of threads", default=8, type=int)
+    p.add_argument("--device", type=int, default=0, help="GPU ordinal")
+    p.add_argument("-v", "--version", action="version", version=VERSION)
+    return p
+
+
+def filter_sequences_main(argv=None):
+    """The filter in front of the overlap stage's sketch (filter_sequences.filter_sequences), FASTA on standard output
+    (bin/ntlink_filter_sequences.py:44-64).  Any error: a message, exit status 1; a contig missing from the FASTA file is found
+    before anything is written."""
+    a = filter_sequences_parser().parse_args(argv)
+    from . import filter_sequences
+    try:
+        dev = _device(a.device)
+        try:
+            sys.stdout.flush()
+            filter_sequences.filter_sequences(a, sys.stdout.fileno(), dev)
+        finally:
+            dev.close()
+    except Exception as exc:
+        print(f"ERROR: {type(exc).__name__}: {exc}", file=sys.stderr)
+        return 1
+    return 0
+
+
 def merge_contigs_parser():
     p = argparse.ArgumentParser(prog="MergeContigs", description="Merge the contigs of a path file into scaffolds (ABySS MergeContigs -k2, "
                                                                  "as `ntLink scaffold` calls it)")

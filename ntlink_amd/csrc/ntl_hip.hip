@@ -41,6 +41,7 @@
 #include "count_kernels.h"
 #include "overlap_kernels.h"
 #include "overlap_cut_kernels.h"
+#include "path_kernels.h"
 #include "format_kernels.h"
 #include "liftover_kernels.h"
 #include "pair_kernels.h"
@@ -2373,6 +2374,123 @@ extern "C" int ntl_overlap_cuts(ntl_ctx *c, const ntl_sketch *s, const ntl_overl
         HIPCHK(c, main_wait(c));
     }
     if (hinfo[2]) return fail(c, NTL_EINTERNAL, "ntl_overlap_cuts: a pair's slices broke the sketch's contract (a hash twice in one sequence, or a probe sequence without an end)");
+    return NTL_OK;
+}
+
+/* ------------------------------------------------------------------ path chains ---------- */
+
+static_assert(sizeof(ntl_path_edge) == sizeof(PathEdge) && sizeof(PathEdge) == 20 && sizeof(ntl_path_link) == sizeof(PathLink) &&
+              sizeof(ntl_path_counts) == sizeof(PathInfo) && sizeof(PathInfo) == 32, "ABI records must match the device records");
+static_assert(NTL_PATH_EDGE_NEW == PATH_EDGE_NEW && NTL_PATH_CONSERVATIVE == PATH_MODE_CONSERVATIVE && NTL_PATH_STITCH == PATH_MODE_STITCH &&
+              NTL_PATH_TRANSITIVE == PATH_MODE_TRANSITIVE, "constants of the ABI and of path_kernels.h");
+
+/* the ranking of the linear graph as it stands -> the buffer that holds it */
+static int path_rank(ntl_ctx *c, const PathArgs &A, unsigned grid, int rounds)
+{
+    hipLaunchKernelGGL(path_rank_init_kernel, dim3(grid), dim3(PATH_NT), 0, c->stream, A);
+    int at = 0;
+    for (int r = 0; r < rounds; r++, at ^= 1) hipLaunchKernelGGL(path_rank_round_kernel, dim3(grid), dim3(PATH_NT), 0, c->stream, A, at);
+    return at;
+}
+
+/* linearize_graph .. remove_duplicate_paths of bin/ntlink_stitch_paths.py:221-365 (path_kernels.h): launches sized by the caller's
+   counts alone -- the doubling rounds by n_vertices -- and ONE wait behind them, for the counts, the error word and the chains.
+   In front of the first launch the host checks every edge's and link's vertex numbers, a serial pass over the caller's arrays. */
+extern "C" int ntl_path_chains(ntl_ctx *c, uint32_t n_vertices, const ntl_path_edge *edges, uint64_t n_edges, const ntl_path_link *links,
+                               uint64_t n_links, uint32_t mode, uint32_t *chain_off, uint32_t *chain_vertex, int32_t *chain_d,
+                               ntl_path_counts *counts)
+{
+    if (!c || !counts || !chain_off || (n_edges && !edges) || (n_links && !links) || (n_vertices && (!chain_vertex || !chain_d))) return NTL_EINVAL;
+    (void)hipSetDevice(c->device);
+    memset(counts, 0, sizeof(*counts));
+    chain_off[0] = 0;
+    if (mode > PATH_MODE_TRANSITIVE) return fail(c, NTL_EINVAL, "ntl_path_chains: mode " + std::to_string(mode) + " is none of conservative, stitch, stitch + transitive");
+    if (n_vertices & 1u) return fail(c, NTL_EINVAL, "ntl_path_chains: n_vertices is odd (a vertex and its twin are 2 * contig and 2 * contig + 1)");
+    if (n_vertices >= (1u << 31) || n_edges >= ((uint64_t)1 << 30) || n_links >= ((uint64_t)1 << 31))
+        return fail(c, NTL_EINVAL, "ntl_path_chains: too many vertices, edges or scaffold-graph edges for one call");
+    for (uint64_t i = 0; i < n_edges; i++) {
+        if (edges[i].src >= n_vertices || edges[i].tgt >= n_vertices)
+            return fail(c, NTL_EINVAL, "ntl_path_chains: edge " + std::to_string(i) + " names a vertex beyond n_vertices");
+        if (edges[i].flags & ~PATH_EDGE_NEW) return fail(c, NTL_EINVAL, "ntl_path_chains: edge " + std::to_string(i) + " has unknown flags");
+    }
+    if (mode != PATH_MODE_TRANSITIVE) n_links = 0; /* the scaffold graph counts for the transitive filter only */
+    for (uint64_t i = 0; i < n_links; i++)
+        if (links[i].a >= n_vertices || links[i].b >= n_vertices)
+            return fail(c, NTL_EINVAL, "ntl_path_chains: scaffold-graph edge " + std::to_string(i) + " names a vertex beyond n_vertices");
+    if (!n_vertices) return NTL_OK;
+    const uint64_t V = n_vertices;
+    int slot_bits = 4, rounds = 0;
+    while (((uint64_t)1 << slot_bits) < 2 * n_edges + 2) slot_bits++;
+    while (((uint64_t)1 << rounds) < V) rounds++;
+    const uint64_t n_slots = (uint64_t)1 << slot_bits;
+    DevBuf dedges, dlinks, slots, slot_edge, sides, graph, words, mins, scans, outs, info;
+    int rc;
+    /* sides: deg, notnew, maxn, cntmax, kept_deg [2V each]; graph: next, prev (0xFF) | vnew, sup, vd, head_of; outs: vertex, d [V], off */
+    if ((rc = dedges.alloc(c, (n_edges + 1) * sizeof(PathEdge))) || (rc = dlinks.alloc(c, (n_links + 1) * sizeof(PathLink))) ||
+        (rc = slots.alloc(c, n_slots * 8)) || (rc = slot_edge.alloc(c, n_slots * 4)) || (rc = sides.alloc(c, 10 * V * 4)) ||
+        (rc = graph.alloc(c, 6 * V * 4)) || (rc = words.alloc(c, 2 * V * 8)) || (rc = mins.alloc(c, 2 * V * 4)) ||
+        (rc = scans.alloc(c, 2 * (V + 1) * 4)) || (rc = outs.alloc(c, (2 * V + V / 2 + 1) * 4)) || (rc = info.alloc(c, sizeof(PathInfo))))
+        return rc;
+    PathArgs A = {};
+    A.n_vertices = n_vertices; A.n_edges = (uint32_t)n_edges; A.n_links = (uint32_t)n_links; A.mode = mode;
+    A.edges = dedges.as<PathEdge>(); A.links = dlinks.as<PathLink>();
+    A.slots = slots.as<unsigned long long>(); A.slot_edge = slot_edge.as<uint32_t>(); A.slot_bits = (uint32_t)slot_bits;
+    A.deg = sides.as<uint32_t>(); A.notnew = A.deg + 2 * V; A.maxn = A.notnew + 2 * V; A.cntmax = A.maxn + 2 * V; A.kept_deg = A.cntmax + 2 * V;
+    A.next = graph.as<uint32_t>(); A.prev = A.next + V; A.vnew = A.prev + V; A.sup = A.vnew + V; A.vd = (int32_t *)(A.sup + V);
+    A.head_of = A.sup + 2 * V;
+    A.word[0] = words.as<unsigned long long>(); A.word[1] = A.word[0] + V;
+    A.minv[0] = mins.as<uint32_t>(); A.minv[1] = A.minv[0] + V;
+    A.lens = scans.as<uint32_t>(); A.cnts = A.lens + V + 1;
+    A.chain_vertex = outs.as<uint32_t>(); A.chain_d = (int32_t *)(A.chain_vertex + V); A.chain_off = A.chain_vertex + 2 * V;
+    A.info = info.as<PathInfo>();
+    PathInfo hinfo = {};
+    const unsigned vgrid = (unsigned)((V + PATH_NT - 1) / PATH_NT), egrid = (unsigned)((n_edges + PATH_NT - 1) / PATH_NT);
+    {
+        ProfSpan sp(c, "paths");
+        if (n_edges) HIPCHK(c, hipMemcpyAsync(dedges.p, edges, n_edges * sizeof(PathEdge), hipMemcpyHostToDevice, c->stream));
+        if (n_links) HIPCHK(c, hipMemcpyAsync(dlinks.p, links, n_links * sizeof(PathLink), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemsetAsync(info.p, 0, sizeof(PathInfo), c->stream));
+        HIPCHK(c, hipMemsetAsync(slots.p, 0xFF, n_slots * 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(sides.p, 0, 10 * V * 4, c->stream));
+        HIPCHK(c, hipMemsetAsync(A.next, 0xFF, 2 * V * 4, c->stream)); /* next, prev = PATH_NONE */
+        HIPCHK(c, hipMemsetAsync(A.vnew, 0, 4 * V * 4, c->stream));
+        if (n_edges) {
+            hipLaunchKernelGGL(path_pass1_kernel, dim3(egrid), dim3(PATH_NT), 0, c->stream, A);
+            hipLaunchKernelGGL(path_pass2_kernel, dim3(egrid), dim3(PATH_NT), 0, c->stream, A);
+            hipLaunchKernelGGL(path_linearize_kernel, dim3(egrid), dim3(PATH_NT), 0, c->stream, A);
+        }
+        int at = path_rank(c, A, vgrid, rounds);
+        if (mode == PATH_MODE_TRANSITIVE) { /* every new edge is judged on the same graph (:363-365), then the graph is ranked again */
+            if (n_links) hipLaunchKernelGGL(path_support_kernel, dim3((unsigned)((n_links + PATH_NT - 1) / PATH_NT)), dim3(PATH_NT), 0, c->stream, A, at);
+            hipLaunchKernelGGL(path_filter_kernel, dim3(vgrid), dim3(PATH_NT), 0, c->stream, A);
+            at = path_rank(c, A, vgrid, rounds);
+        }
+        hipLaunchKernelGGL(path_heads_kernel, dim3(vgrid), dim3(PATH_NT), 0, c->stream, A, at);
+        HIPCHK(c, hipGetLastError());
+        if ((rc = device_scan(c, A.lens, A.lens, V, nullptr, 2, &A.info->n_chain_vertices))) return rc;
+        hipLaunchKernelGGL(path_scatter_kernel, dim3(vgrid), dim3(PATH_NT), 0, c->stream, A, at);
+        HIPCHK(c, hipGetLastError());
+    }
+    /* the result comes back through the context's page-locked block: two copies that do not block, ONE wait, and only what the
+       counts say goes on to the caller's arrays */
+    const size_t out_bytes = (2 * V + V / 2 + 1) * 4;
+    void *stage = nullptr;
+    if ((rc = host_tmp(c, out_bytes + sizeof(PathInfo), &stage))) return rc;
+    uint32_t *h_vertex = (uint32_t *)stage, *h_d = h_vertex + V, *h_off = h_vertex + 2 * V;
+    HIPCHK(c, hipMemcpyAsync(stage, outs.p, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync((char *)stage + out_bytes, info.p, sizeof(PathInfo), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, main_wait(c));
+    memcpy(&hinfo, (char *)stage + out_bytes, sizeof(PathInfo));
+    if (hinfo.err & PATH_ERR_DUP) return fail(c, NTL_EINVAL, "ntl_path_chains: an edge occurs twice in the edge list");
+    if (hinfo.err & PATH_ERR_TWIN)
+        return fail(c, NTL_EINVAL, "ntl_path_chains: an edge lacks its twin (tgt ^ 1, src ^ 1) with the same d, n and flags");
+    if (hinfo.err & PATH_ERR_NONLINEAR) return fail(c, NTL_EINVAL, "ntl_path_chains: graph is not linear after linearize");
+    if (hinfo.n_chain_vertices > V || hinfo.n_chains > V / 2) return fail(c, NTL_EINTERNAL, "ntl_path_chains: the chains do not fit the graph");
+    memcpy(chain_vertex, h_vertex, (size_t)hinfo.n_chain_vertices * 4);
+    memcpy(chain_d, h_d, (size_t)hinfo.n_chain_vertices * 4);
+    memcpy(chain_off, h_off, ((size_t)hinfo.n_chains + 1) * 4);
+    memcpy(counts, &hinfo, sizeof(*counts));
+    counts->reserved[0] = counts->reserved[1] = counts->reserved[2] = 0;
     return NTL_OK;
 }
 
