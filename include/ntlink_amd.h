@@ -172,7 +172,9 @@ void ntl_host_free(ntl_ctx *ctx, void *p);
  *       per-base event probabilities (0,0,0 = exact copy: contigs).  With errors the slice may consume up
  *       to out_len + out_len/8 + 64 source bases, which must fit the source sequence.
  *   ntl_batch_download: the bases back as ASCII (seqs[offsets[i]..offsets[i+1]), offsets[nseq+1]) --
- *       what the tests hand to the oracle.  Only for pure-ACGT batches. */
+ *       what the tests hand to the oracle.  Only for pure-ACGT batches: every sequence non-empty and one ACGT run from its
+ *       first base to its last, however the batch was made (NTL_EINVAL otherwise; ntl_batch_download_n takes any batch).
+ *       ntl_synth_slices asks the same of its source batch. */
 int ntl_synth_genome(ntl_ctx *ctx, uint64_t seed, const uint32_t *len, uint64_t nseq, ntl_batch **out);
 int ntl_synth_slices(ntl_ctx *ctx, const ntl_batch *src, uint64_t seed, uint64_t n, const uint32_t *src_seq,
                      const uint32_t *src_start, const uint32_t *out_len, const uint8_t *reverse,

@@ -7,7 +7,8 @@
  * plus a table of ACGT runs, so the masked copy of a record is the same bases with the run table clipped to [keep_lo, keep_hi):
  *
  *   nmask_count_kernel   a lane per output record: the source record's runs that intersect the range (two binary searches in its
- *                       slice of the run table) -> cnt, first; their sum and "some record keeps more than one run" -> stats
+ *                       slice of the run table) -> cnt, first; their sum, "some record keeps more than one run" and
+ *                       "some record is not one whole run" -> stats
  *   (device_scan over cnt -> the output's seq_run_first)
  *   nmask_fill_kernel    a lane per output record: its runs, clipped to the range
  *   nmask_copy_kernel    a wavefront per output record: the packed words of the range, a lane per destination word.  Source and
@@ -38,8 +39,11 @@ struct MaskArgs {
     uint32_t *first;                   /* [n]: the first kept run, in the source's table */
     const uint32_t *dst_seq_run_first; /* [n+1] */
     uint32_t *dst_run_start, *dst_run_len;
-    unsigned long long *stats;         /* [0] runs kept in all (64 bits: the scan's sum is 32), [1] != 0: a record keeps several */
+    unsigned long long *stats;         /* [0] runs kept in all (64 bits: the scan's sum is 32), [1] NMASK_* bits */
 };
+
+#define NMASK_MULTI 1ull  /* a record keeps several runs */
+#define NMASK_IMPURE 2ull /* a record is not one run from its first base to its last */
 
 /* first run r of [r0, r1) with run_start[r] + run_len[r] > pos (ends ascend); r1 if none */
 __device__ __forceinline__ uint32_t nmask_first_end_above(const uint32_t *run_start, const uint32_t *run_len, uint32_t r0, uint32_t r1, uint32_t pos)
@@ -77,7 +81,14 @@ __global__ __launch_bounds__(MASK_NT) void nmask_count_kernel(MaskArgs A)
     A.cnt[i] = c;
     A.first[i] = a;
     if (c) atomicAdd(&A.stats[0], (unsigned long long)c);
-    if (c > 1u) atomicOr(&A.stats[1], 1ull);
+    unsigned long long f = c > 1u ? NMASK_MULTI : 0ull;
+    bool whole = false; /* the record is one kept run that the range does not clip: from base 0 to its length */
+    if (c == 1u) {
+        const uint64_t len = A.dst_seq_base[i + 1] - A.dst_seq_base[i];
+        whole = lo == 0 && A.src_run_start[a] == 0 && hi == len && A.src_run_len[a] == len;
+    }
+    if (!whole) f |= NMASK_IMPURE;
+    if (f) atomicOr(&A.stats[1], f);
 }
 
 __global__ __launch_bounds__(MASK_NT) void nmask_fill_kernel(MaskArgs A)

@@ -523,6 +523,8 @@ struct ntl_batch {
     std::atomic<int> refs{1}; /* the caller's + one per sketch that may still have to be redone from it (sketch_finalize) */
     uint64_t nseq = 0, bases = 0, nruns = 0, total_gpos = 0, nwords_packed = 0;
     bool any_multi = false; /* some sequence has more than one ACGT run */
+    bool pure = false;      /* every sequence is one ACGT run from its first base to its last (so none is empty): decided where the
+                               batch is made, read by ntl_batch_download and ntl_synth_slices */
     DevBuf packed, seq_base, seq_run_first, run_start, run_len;
     DevBuf seq_len_dev;             /* u32[nseq]: the `--len` column of the batch's sequences (unset where run_len already is that) */
     const uint32_t *d_seq_len = nullptr;
@@ -624,13 +626,13 @@ extern "C" int ntl_batch_create(ntl_ctx *c, const char *seqs, const uint64_t *of
     const uint64_t n32 = (NTL_LEAD_PAD + total + 31) / 32; /* threads = 32-position groups that hold data */
     int rc;
     (void)hipSetDevice(c->device);
-    DevBuf raw, valid32, ss32, starts32, rank, any_multi;
+    DevBuf raw, valid32, ss32, starts32, rank, flags;
     if ((rc = b->packed.alloc(c, nwords * 4)) || (rc = b->seq_base.alloc(c, (nseq + 1) * 8)) ||
         (rc = b->seq_run_first.alloc(c, (nseq + 1) * 4)) || (rc = raw.alloc(c, total + 64)) ||
         (rc = valid32.alloc(c, (n32 + 2) * 4)) || (rc = ss32.alloc(c, (n32 + 2) * 4)) ||
-        (rc = starts32.alloc(c, (n32 + 2) * 4)) || (rc = rank.alloc(c, (n32 + 2) * 4)) || (rc = any_multi.alloc(c, 4)))
+        (rc = starts32.alloc(c, (n32 + 2) * 4)) || (rc = rank.alloc(c, (n32 + 2) * 4)) || (rc = flags.alloc(c, 4)))
         return rc;
-    uint32_t nruns = 0, multi = 0;
+    uint32_t nruns = 0, seen = 0;
     DevBuf start_g, end_g;
     {
     ProfSpan span(c, "batch_pack");
@@ -642,7 +644,7 @@ extern "C" int ntl_batch_create(ntl_ctx *c, const char *seqs, const uint64_t *of
     HIPCHK(c, hipMemsetAsync(ss32.p, 0, (n32 + 2) * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(starts32.p, 0, (n32 + 2) * 4, c->stream));
     HIPCHK(c, hipMemsetAsync(rank.p, 0, (n32 + 2) * 4, c->stream)); /* counts; scanned in place */
-    HIPCHK(c, hipMemsetAsync(any_multi.p, 0, 4, c->stream));
+    HIPCHK(c, hipMemsetAsync(flags.p, 0, 4, c->stream));
     const unsigned g32 = (unsigned)((n32 + PACK_NT - 1) / PACK_NT);
     const unsigned gseq = (unsigned)((nseq + 1 + PACK_NT - 1) / PACK_NT);
     if (n32) {
@@ -669,14 +671,24 @@ extern "C" int ntl_batch_create(ntl_ctx *c, const char *seqs, const uint64_t *of
                            b->run_len.as<uint32_t>());
     }
     hipLaunchKernelGGL(seq_runs_kernel, dim3(gseq), dim3(PACK_NT), 0, c->stream, starts32.as<uint32_t>(), rank.as<uint32_t>(),
-                       b->seq_base.as<uint64_t>(), (uint32_t)nseq, b->seq_run_first.as<uint32_t>(), any_multi.as<uint32_t>());
+                       b->seq_base.as<uint64_t>(), (uint32_t)nseq, b->run_len.as<uint32_t>(), b->seq_run_first.as<uint32_t>(),
+                       flags.as<uint32_t>());
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(&multi, any_multi.p, 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&seen, flags.p, 4, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(c, hipStreamSynchronize(c->stream)); /* the caller's arrays and seq_base are free again */
-    b->any_multi = multi != 0;
+    b->any_multi = (seen & SEQ_RUNS_MULTI) != 0;
+    b->pure = (seen & SEQ_RUNS_IMPURE) == 0;
     *out = b.release();
     return NTL_OK;
+}
+
+/* ntl_batch::pure of a run table that arrives from the host (seq_run_first checked: non-decreasing, ends at the run count) */
+static bool host_runs_pure(const uint32_t *len, uint64_t nseq, const uint32_t *seq_run_first, const uint32_t *run_len)
+{
+    for (uint64_t i = 0; i < nseq; i++)
+        if (seq_run_first[i + 1] - seq_run_first[i] != 1u || run_len[seq_run_first[i]] != len[i]) return false;
+    return true;
 }
 
 /* The same batch from bases that are already packed (ntl_fastx_copy_packed + ntl_fastx_runs: the parser threads pack
@@ -705,6 +717,7 @@ extern "C" int ntl_batch_create_packed(ntl_ctx *c, const uint32_t *packed, const
     if (seq_run_first[0] != 0 || seq_run_first[nseq] != nruns) return fail(c, NTL_EINVAL, "seq_run_first does not match the run count");
     seq_base[nseq] = NTL_LEAD_PAD + off[nseq];
     b->nruns = nruns; b->any_multi = multi;
+    b->pure = host_runs_pure(b->seq_len.data(), nseq, seq_run_first, run_len);
     if (int rc = batch_upload_packed(c, b.get(), packed, seq_base, seq_run_first, run_start, run_len)) return rc;
     *out = b.release();
     return NTL_OK;
@@ -739,6 +752,7 @@ extern "C" int ntl_batch_create_packed_at(ntl_ctx *c, const uint32_t *packed, ui
     std::unique_ptr<ntl_batch> b = batch_new(c, nseq, total, span_positions);
     b->seq_len.assign(lengths, lengths + nseq);
     b->nruns = nruns; b->any_multi = multi;
+    b->pure = host_runs_pure(lengths, nseq, seq_run_first, run_len);
     if (int rc = batch_upload_packed(c, b.get(), packed, seq_base, seq_run_first, run_start, run_len)) return rc;
     *out = b.release();
     return NTL_OK;
@@ -781,6 +795,7 @@ static int synth_layout(ntl_ctx *c, const uint32_t *len, uint64_t nseq, std::uni
     b = batch_new(c, nseq, total, total);
     b->seq_len.assign(len, len + nseq);
     b->nruns = nseq;
+    b->pure = true;
     int rc;
     if ((rc = b->packed.alloc(c, b->nwords_packed * 4)) || (rc = b->seq_base.alloc(c, (nseq + 1) * 8)) ||
         (rc = b->seq_run_first.alloc(c, (nseq + 1) * 4)) || (rc = b->run_start.alloc(c, (nseq + 1) * 4)) ||
@@ -820,7 +835,7 @@ extern "C" int ntl_synth_slices(ntl_ctx *c, const ntl_batch *src, uint64_t seed,
 {
     if (!c || !src || !out || (n && (!src_seq || !src_start || !out_len))) return NTL_EINVAL;
     *out = nullptr;
-    if (src->nruns != src->nseq || src->any_multi) return fail(c, NTL_EINVAL, "the source batch must be pure ACGT");
+    if (!src->pure) return fail(c, NTL_EINVAL, "the source batch must be pure ACGT");
     if (sub < 0 || ins < 0 || del < 0 || sub > 0.5 || ins + del > 0.5) return fail(c, NTL_EINVAL, "error rates out of range");
     const bool errors = sub > 0 || ins > 0 || del > 0;
     for (uint64_t i = 0; i < n; i++) {
@@ -860,7 +875,7 @@ extern "C" int ntl_batch_download(const ntl_batch *b, char *seqs, uint64_t *off)
 {
     if (!b || (!seqs && b->bases) || !off) return NTL_EINVAL;
     ntl_ctx *c = b->c;
-    if (b->nruns != b->nseq || b->any_multi) return fail(c, NTL_EINVAL, "only pure-ACGT batches can be downloaded");
+    if (!b->pure) return fail(c, NTL_EINVAL, "only pure-ACGT batches can be downloaded");
     (void)hipSetDevice(c->device);
     uint64_t t = 0;
     for (uint64_t i = 0; i < b->nseq; i++) { off[i] = t; t += b->seq_len[i]; }
@@ -951,7 +966,8 @@ extern "C" int ntl_batch_mask(ntl_ctx *c, const ntl_batch *src, uint64_t n, cons
     HIPCHK(c, hipStreamSynchronize(c->stream)); /* the run count: the size of the run tables */
     if (stats[0] >= 0xFFFFFFF0ull) return fail(c, NTL_EINVAL, "too many ACGT runs in one batch");
     b->nruns = stats[0];
-    b->any_multi = stats[1] != 0;
+    b->any_multi = (stats[1] & NMASK_MULTI) != 0;
+    b->pure = (stats[1] & NMASK_IMPURE) == 0;
     if ((rc = b->run_start.alloc(c, (b->nruns + 1) * 4)) || (rc = b->run_len.alloc(c, (b->nruns + 1) * 4))) return rc;
     if (b->nruns) {
         ProfSpan span(c, "batch_mask");

@@ -19,7 +19,7 @@
  *                      and the i-th end belong to the same run
  *   run_finish_kernel  per run: owning sequence (binary search of seq_base), offset in it, length
  *   seq_runs_kernel    per sequence: seq_run_first = rank of its first gpos; flags a sequence
- *                      with more than one run
+ *                      with more than one run, and one that is not a single run of its whole length
  */
 #pragma once
 #include "dev_common.h"
@@ -141,13 +141,21 @@ __device__ __forceinline__ uint32_t run_rank_at(const uint32_t *starts32, const 
     return rank[t] + (uint32_t)__popc(starts32[t] & ((1u << j) - 1u));
 }
 
-/* s in [0, nseq]; starts32 / rank are defined (zero count) for the padding word after the data */
+#define SEQ_RUNS_MULTI 1u  /* some sequence has more than one run */
+#define SEQ_RUNS_IMPURE 2u /* some sequence is not one run from its first base to its last (an empty one has no run) */
+
+/* s in [0, nseq]; starts32 / rank are defined (zero count) for the padding word after the data; run_len is complete
+   (run_finish_kernel ran before); flags is zero-filled */
 __global__ __launch_bounds__(PACK_NT) void seq_runs_kernel(const uint32_t *starts32, const uint32_t *rank, const uint64_t *seq_base,
-                                                           uint32_t nseq, uint32_t *seq_run_first, uint32_t *any_multi)
+                                                           uint32_t nseq, const uint32_t *run_len, uint32_t *seq_run_first, uint32_t *flags)
 {
     const uint32_t s = blockIdx.x * PACK_NT + threadIdx.x;
     if (s > nseq) return;
     const uint32_t a = run_rank_at(starts32, rank, seq_base[s]);
     seq_run_first[s] = a;
-    if (s < nseq && run_rank_at(starts32, rank, seq_base[s + 1]) - a > 1u) atomicOr(any_multi, 1u);
+    if (s == nseq) return;
+    const uint32_t n = run_rank_at(starts32, rank, seq_base[s + 1]) - a;
+    uint32_t f = n > 1u ? SEQ_RUNS_MULTI : 0u;
+    if (n != 1u || (uint64_t)run_len[a] != seq_base[s + 1] - seq_base[s]) f |= SEQ_RUNS_IMPURE;
+    if (f) atomicOr(flags, f);
 }
