@@ -215,7 +215,7 @@ template <typename IT> struct RunArr { uint32_t *ctg, *mn, *mx; IT *start, *lead
 #define RF_SUB 2u
 #define AX_DUP 1u
 #define AX_FILT 2u
-#define AX_BRK 4u
+#define AX_BRK 4u /* no entry gets AX_FILT and AX_BRK both, and the first gets neither (tests/test_paf_blocks.py) */
 
 /* flags of the PAF stage, set by several lanes on neighbouring entries: a 32-bit atomic on the word that holds the entry */
 __device__ __forceinline__ void map_ax_or(uint32_t *aux, uint32_t i, uint32_t bits) { atomicOr(&aux[i], bits); }
