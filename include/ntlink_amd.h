@@ -38,6 +38,8 @@
  *   ntl_write_*   indexlr TSV / verbose / PAF text  <- indexlr stdout (ntLink:199,223),
  *                                                      bin/ntlink_pair.py:308-313,382-388,
  *                                                      bin/ntlink_paf_output.py:131-135
+ *   ntl_sketch_format  indexlr's TSV from a resident  <- indexlr's printing (ntLink:199,223,244,249)
+ *                 sketch, on the device
  *   ntl_tally_*   contig-pair tally                 <- bin/ntlink_pair.py:416-435,315-334,157-239
  *   ntl_liftover  verbose mappings through an AGP   <- bin/ntlink_liftover_mappings.py:61-143 (ntLink_rounds:124-125)
  *   ntl_mapres_liftover  the same on a resident     <- liftover_ctg_mappings, print_adjusted_mappings (:61-121)
@@ -69,7 +71,8 @@
  * NTL_SIDE_STREAM (1: a third stream for the window stage's give-up passes, beside the next sketch's window kernel; 2: a sketch's
  * preparation on it too; default 0: both stay on the window stream; NTL_SIDE_PRIO=0: that stream at the window stream's priority
  * instead of MAIN's),
- * NTL_SKETCH_CAP_GUESS (records a sketch's arrays hold before its count is known; tests force the second round with it).
+ * NTL_SKETCH_CAP_GUESS (records a sketch's arrays hold before its count is known; tests force the second round with it),
+ * NTL_SKETCH_TEXT_MAX_BYTES (lowers the bytes one ntl_sketch_format call may make; tests cut small sketches into pieces with it).
  */
 #ifndef NTLINK_AMD_H
 #define NTLINK_AMD_H
@@ -749,6 +752,36 @@ int ntl_text_download(const ntl_text *t, char *verbose, char *paf, ntl_mapping *
 void ntl_text_destroy(ntl_text *t);
 /* n bytes at the end of fd (O_APPEND or not: the position is taken once), written by the I/O worker pool in parallel pieces. */
 int ntl_write_blob(int fd, const char *p, uint64_t n);
+
+/* ---- indexlr's TSV, made on the device ---------------------------------------------------------
+ * Replaces indexlr's printing (`indexlr --long --pos --strand [--len]`, ntLink:199,223; the `H:pos` form of the overlap stage,
+ * `indexlr --long --pos -k 15 -w 5`, ntLink:244,249): the lines `id\t[len\t]H:pos[:strand] ...` are laid out and written by kernels
+ * (csrc/sketch_text_kernels.h) from the records of a resident sketch and a name table that lives on the device; what crosses PCIe is
+ * the text itself.  The bytes are those of ntl_write_indexlr on the sketch's downloaded columns; a sequence without a minimizer has
+ * its line `id\t[len\t]\n` there too.
+ *
+ * ntl_sketch_format completes the sketch (waits for it), then formats the lines of the sequences [seq_lo, seq_hi): name i of `names`
+ * and its length belong to sequence i of the sketch.  flags: NTL_SKETCH_TEXT_LEN the `--len` column, NTL_SKETCH_TEXT_STRAND the
+ * `--strand` column (clear it for `H:pos`).  One host wait inside, for the byte total that sizes the text; the first call on a
+ * sketch also fetches its nseq + 1 offsets once, since a range's minimizers size the work.  The text keeps what it needs: sketch
+ * and names may be destroyed once the call has returned.  Event name for ntl_prof_get: "sketch_text".
+ * Offsets inside one text are 32 bits, so the CALLER cuts a sketch into ranges: a range is taken iff ntl_sketch_text_bound(names,
+ * its sequences, its minimizers) -- 34 bytes per minimizer, the longest name + 13 per sequence -- is below ntl_sketch_text_limit()
+ * (2^32 - 256, or NTL_SKETCH_TEXT_MAX_BYTES where that is less: a test hook).  A single sequence above the limit is refused, not split.
+ *   NTL_EINVAL with a message: a sketch without records (ntl_sketch_has_records() == 0), a name table with fewer names than the
+ *   sketch has sequences or on another device, NTL_SKETCH_TEXT_LEN with a table made without lengths, seq_lo > seq_hi, seq_hi beyond
+ *   the sketch, unknown flag bits.  NTL_ERANGE with a message: the range's bound reaches the limit; nothing is queued, nothing written.
+ * A text offers its byte count, a download into caller memory (waits) and a destroy -- a handle of its own and not an ntl_text, whose
+ * sizes and download speak of a map result's two files, its mappings and its hit ends. */
+typedef struct ntl_sktext ntl_sktext;
+#define NTL_SKETCH_TEXT_LEN 1
+#define NTL_SKETCH_TEXT_STRAND 2
+int ntl_sketch_format(const ntl_sketch *s, const ntl_names *names, int flags, uint64_t seq_lo, uint64_t seq_hi, ntl_sktext **out);
+uint64_t ntl_sketch_text_limit(void);
+uint64_t ntl_sketch_text_bound(const ntl_names *names, uint64_t n_seq, uint64_t n_mx);
+uint64_t ntl_sktext_bytes(const ntl_sktext *t);
+int ntl_sktext_download(const ntl_sktext *t, char *out);
+void ntl_sktext_destroy(ntl_sktext *t);
 
 /* ---- host-side pair tally (no GPU involved) ------------------------------------------------- */
 

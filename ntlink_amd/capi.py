@@ -37,6 +37,7 @@ SYMBOLS = [
     "ntl_tally_create", "ntl_tally_destroy", "ntl_tally_add", "ntl_tally_npairs", "ntl_tally_ngaps", "ntl_tally_export", "ntl_tally_merge",
     "ntl_liftover",
     "ntl_names_create", "ntl_names_destroy", "ntl_mapres_format", "ntl_text_sizes", "ntl_text_download", "ntl_text_destroy", "ntl_write_blob",
+    "ntl_sketch_format", "ntl_sketch_text_limit", "ntl_sketch_text_bound", "ntl_sktext_bytes", "ntl_sktext_download", "ntl_sktext_destroy",
     "ntl_tally_add_ends", "ntl_tally_write", "ntl_io_errno",
     "ntl_pairtab_create", "ntl_pairtab_destroy", "ntl_mapres_pairs", "ntl_pairs_count", "ntl_pairs_download", "ntl_pairs_destroy", "ntl_tally_add_pairs",
 ]
@@ -69,6 +70,8 @@ NTL_LIFT_LANE_LINES = 16
 PAIR_REC_DT = np.dtype([("src", "<u4"), ("tgt", "<u4"), ("gap", "<i8"), ("read", "<u4"), ("src_ori", "u1"), ("tgt_ori", "u1"), ("anchor", "u1"),
                         ("pad", "u1")])  # ntl_pair_rec
 NTL_PAIR_LANE_MAPS = 16
+NTL_SKETCH_TEXT_LEN, NTL_SKETCH_TEXT_STRAND = 1, 2  # flags of ntl_sketch_format
+SKETCH_TEXT_PIECE = 256 << 20  # bound of one piece of Sketch.text: what the drain thread writes while the next piece is formatted
 NO_CTG = 0xFFFFFFFF  # ntl_mapping.ctg of a name that is not in the reader's table
 
 
@@ -274,6 +277,16 @@ def load(path=None):
     L.ntl_text_destroy.argtypes = [vp]
     L.ntl_text_destroy.restype = None
     L.ntl_write_blob.argtypes = [C.c_int, vp, C.c_uint64]
+    L.ntl_sketch_format.argtypes = [vp, vp, C.c_int, C.c_uint64, C.c_uint64, C.POINTER(vp)]
+    L.ntl_sketch_text_limit.argtypes = []
+    L.ntl_sketch_text_limit.restype = C.c_uint64
+    L.ntl_sketch_text_bound.argtypes = [vp, C.c_uint64, C.c_uint64]
+    L.ntl_sketch_text_bound.restype = C.c_uint64
+    L.ntl_sktext_bytes.argtypes = [vp]
+    L.ntl_sktext_bytes.restype = C.c_uint64
+    L.ntl_sktext_download.argtypes = [vp, vp]
+    L.ntl_sktext_destroy.argtypes = [vp]
+    L.ntl_sktext_destroy.restype = None
     for nm in ("npairs", "ngaps"):
         f = getattr(L, "ntl_tally_" + nm)
         f.argtypes = [vp]
@@ -453,6 +466,62 @@ class Sketch(_Handle):
         self.dev._chk(self.dev.L.ntl_sketch_download(self.ptr, _ptr(off, C.c_uint64), _ptr(h, C.c_uint64),
                                                      _ptr(p, C.c_uint32), _ptr(s, C.c_uint8)))
         return off, h, p, s
+
+    def offsets(self):
+        """mx_off u64[nseq+1] alone (no record crosses PCIe)."""
+        self.wait()
+        off = np.zeros(self.nseq + 1, np.uint64)
+        self.dev._chk(self.dev.L.ntl_sketch_download(self.ptr, _ptr(off, C.c_uint64), None, None, None))
+        return off
+
+    def format(self, names, with_len, with_strand=True, seq_lo=0, seq_hi=None):
+        """The lines of the sequences [seq_lo, seq_hi) of indexlr's TSV, made on the device (ntl_sketch_format): one call, one
+        SketchText.  names: the NameTable (Device.names) of the batch's names and lengths.  NtlError with .code NTL_ERANGE where
+        the range's bound reaches the limit of one call: Sketch.text cuts."""
+        flags = (NTL_SKETCH_TEXT_LEN if with_len else 0) | (NTL_SKETCH_TEXT_STRAND if with_strand else 0)
+        p = C.c_void_p()
+        self.dev._chk(self.dev.L.ntl_sketch_format(self.ptr, names.ptr, flags, int(seq_lo), int(self.nseq if seq_hi is None else seq_hi), C.byref(p)))
+        return SketchText(self.dev, p)
+
+    def text_ranges(self, names, piece_bytes=None):
+        """The ranges [lo, hi) Sketch.text formats, in order -- the one place where a sketch is cut: each the longest run of whole
+        sequences whose bound (ntl_sketch_text_bound: 34 bytes per minimizer, the longest name + 13 per sequence) stays below the
+        limit of one call (ntl_sketch_text_limit) and below piece_bytes (default SKETCH_TEXT_PIECE).  A sequence that alone reaches
+        the limit is a range of its own: the call refuses it (NTL_ERANGE), it is not split."""
+        L = self.dev.L
+        limit = min(int(L.ntl_sketch_text_limit()), int(SKETCH_TEXT_PIECE if piece_bytes is None else piece_bytes))
+        per_seq, per_mx = int(L.ntl_sketch_text_bound(names.ptr, 1, 0)), int(L.ntl_sketch_text_bound(names.ptr, 0, 1))
+        nseq = self.nseq
+        cum = self.offsets().astype(np.int64) * per_mx + np.arange(nseq + 1, dtype=np.int64) * per_seq  # the bound of [0, i)
+        out, lo = [], 0
+        while lo < nseq:
+            hi = int(np.searchsorted(cum, cum[lo] + limit, side="left")) - 1  # the last hi with cum[hi] - cum[lo] < limit
+            hi = max(hi, lo + 1)
+            out.append((lo, hi))
+            lo = hi
+        return out
+
+    def text(self, names, with_len, with_strand=True, piece_bytes=None):
+        """indexlr's TSV of this sketch, made on the device: yields its pieces in sequence order, each a uint8 array in page-locked
+        memory of the device's pool (hand it to Device.pinned_release() when it has been written).  No record is downloaded."""
+        for lo, hi in self.text_ranges(names, piece_bytes):
+            with self.format(names, with_len, with_strand, lo, hi) as t:
+                yield t.download()
+
+
+class SketchText(_Handle):
+    """Lines of indexlr's TSV of one range of a sketch's sequences, formatted on the device."""
+    _destroy = "ntl_sktext_destroy"
+
+    @property
+    def nbytes(self):
+        return int(self.dev.L.ntl_sktext_bytes(self.ptr))
+
+    def download(self):
+        """The bytes as a uint8 array in a page-locked buffer of the device's pool (Device.pinned_release() gives it back)."""
+        buf = self.dev.pinned_empty(self.nbytes)
+        self.dev._chk(self.dev.L.ntl_sktext_download(self.ptr, buf.ctypes.data if len(buf) else None))
+        return buf
 
 
 class Index(_Handle):

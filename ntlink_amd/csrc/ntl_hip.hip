@@ -43,6 +43,7 @@
 #include "overlap_cut_kernels.h"
 #include "path_kernels.h"
 #include "format_kernels.h"
+#include "sketch_text_kernels.h"
 #include "liftover_kernels.h"
 #include "pair_kernels.h"
 #include "tally_view.h"
@@ -1235,6 +1236,8 @@ struct ntl_sketch {
     mutable uint64_t nfound = 0;
     mutable DevBuf records; /* MxRecord[cap] */
     mutable DevBuf mx_off;  /* u32[nseq+1] */
+    mutable std::vector<uint32_t> h_off; /* the host's copy of mx_off, or empty: fetched by the first ntl_sketch_format (the ranges'
+                                            minimizer counts size its work), kept for the next ranges of the same sketch */
     mutable uint64_t cap = 0;             /* records the arrays can hold */
     /* ntl_sketch_run_indexed: the minimizers were looked up in index cand_gen while they were emitted */
     uint64_t cand_gen = 0;
@@ -3516,6 +3519,113 @@ extern "C" int ntl_text_download(const ntl_text *t, char *verbose, char *paf, nt
 }
 
 extern "C" void ntl_text_destroy(ntl_text *t)
+{
+    if (!t) return;
+    (void)hipSetDevice(t->c->device);
+    delete t;
+}
+
+/* ------------------------------------------------------------------ a sketch's text on the device ---- */
+
+/* One text, one size: a sibling of ntl_text, whose sizes and download speak of a map result's two files, mappings and hit ends. */
+struct ntl_sktext {
+    ntl_ctx *c;
+    uint64_t bytes = 0;
+    DevBuf text;
+};
+
+extern "C" uint64_t ntl_sketch_text_limit(void)
+{
+    uint64_t most = 0xFFFFFF00ull; /* 32-bit offsets */
+    if (const char *e = getenv("NTL_SKETCH_TEXT_MAX_BYTES")) most = std::min<uint64_t>(most, strtoull(e, nullptr, 10)); /* tests: pieces without 4 GB of text */
+    return most;
+}
+
+extern "C" uint64_t ntl_sketch_text_bound(const ntl_names *names, uint64_t n_seq, uint64_t n_mx)
+{
+    return n_mx * SKTEXT_TOKEN_MAX + n_seq * ((names ? names->max_len : 0) + SKTEXT_HEADER_EXTRA);
+}
+
+/* The length pass, two scans and the fill pass on MAIN (sketch_text_kernels.h), every temporary a block of the context's cache.  ONE wait
+   between the scans and the fill: the two totals land in a page-locked slot (pending.h) and size the text.  The first call on a sketch
+   also fetches its nseq + 1 offsets, once: the minimizers of a range size the launches and bound its bytes. */
+extern "C" int ntl_sketch_format(const ntl_sketch *s, const ntl_names *names, int flags, uint64_t seq_lo, uint64_t seq_hi, ntl_sktext **out)
+{
+    if (!s || !names || !out) return NTL_EINVAL;
+    *out = nullptr;
+    ntl_ctx *c = s->c;
+    (void)hipSetDevice(c->device);
+    if (flags & ~(NTL_SKETCH_TEXT_LEN | NTL_SKETCH_TEXT_STRAND)) return fail(c, NTL_EINVAL, "ntl_sketch_format: unknown flag bits");
+    if (s->no_records) return fail(c, NTL_EINVAL, "ntl_sketch_format: a sketch made by ntl_sketch_run_for_map holds no records");
+    if (names->c->device != c->device) return fail(c, NTL_EINVAL, "ntl_sketch_format: the name table lives on another device");
+    if (names->n < s->nseq) return fail(c, NTL_EINVAL, "ntl_sketch_format: the name table holds fewer names than the sketch has sequences");
+    if (seq_lo > seq_hi || seq_hi > s->nseq)
+        return fail(c, NTL_EINVAL, "ntl_sketch_format: the range [" + std::to_string(seq_lo) + ", " + std::to_string(seq_hi) + ") is not one of the sketch's " +
+                                       std::to_string(s->nseq) + " sequences");
+    if ((flags & NTL_SKETCH_TEXT_LEN) && names->n && !names->len.p) return fail(c, NTL_EINVAL, "ntl_sketch_format: the length column needs a name table with lengths");
+    if (int frc = sketch_finalize(s)) return fail(c, frc, "ntl_sketch_format: the sketch failed: " + c->err);
+    if (s->h_off.empty()) {
+        s->h_off.resize(s->nseq + 1);
+        hipError_t e = hipMemcpyAsync(s->h_off.data(), s->mx_off.p, (s->nseq + 1) * 4, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = main_wait(c);
+        if (e != hipSuccess) { s->h_off.clear(); return fail(c, NTL_EDEVICE, std::string("ntl_sketch_format: ") + hipGetErrorString(e)); }
+    }
+    const uint64_t n_seq = seq_hi - seq_lo, n_mx = s->h_off[seq_hi] - s->h_off[seq_lo];
+    const uint64_t bound = ntl_sketch_text_bound(names, n_seq, n_mx), most = ntl_sketch_text_limit();
+    if (bound >= most)
+        return fail(c, NTL_ERANGE, "ntl_sketch_format: the text of sequences [" + std::to_string(seq_lo) + ", " + std::to_string(seq_hi) + ") may take " +
+                                       std::to_string(bound) + " bytes, one call makes fewer than " + std::to_string(most) +
+                                       " (32-bit offsets; NTL_SKETCH_TEXT_MAX_BYTES): format fewer sequences per call");
+    std::unique_ptr<ntl_sktext> t(new ntl_sktext());
+    t->c = c;
+    if (!n_seq) { *out = t.release(); return NTL_OK; }
+    DevBuf tok, hdr;
+    int rc;
+    if ((rc = tok.alloc(c, (n_mx + 1) * 4)) || (rc = hdr.alloc(c, (n_seq + 1) * 4))) return rc;
+    SkTextArgs A = {};
+    A.recs = s->records.as<MxRecord>(); A.mx_off = s->mx_off.as<uint32_t>();
+    A.name_off = names->off.as<uint64_t>(); A.names = names->blob.as<char>(); A.seq_len = names->len.as<uint32_t>();
+    A.seq_lo = (uint32_t)seq_lo; A.n_seq = (uint32_t)n_seq; A.mx_lo = s->h_off[seq_lo]; A.n_mx = (uint32_t)n_mx;
+    A.with_len = flags & NTL_SKETCH_TEXT_LEN ? 1 : 0; A.with_strand = flags & NTL_SKETCH_TEXT_STRAND ? 1 : 0;
+    A.tok_len = tok.as<uint32_t>(); A.hdr_len = hdr.as<uint32_t>(); A.text = nullptr;
+    const unsigned grid = (unsigned)((std::max(n_mx, n_seq) + SKTEXT_NT - 1) / SKTEXT_NT);
+    Pending p;
+    if (!p.arm(c->pq)) return fail(c, NTL_EDEVICE, "ntl_sketch_format: no free result slot (too many pending results)");
+    uint32_t *totals = (uint32_t *)c->pq.slot_dev(p.slot); /* [0] the tokens' bytes, [1] the headers' */
+    ProfSpan sp(c, "sketch_text");
+    hipLaunchKernelGGL((sktext_kernel<false>), dim3(grid), dim3(SKTEXT_NT), 0, c->stream, A);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && ((rc = device_scan(c, A.tok_len, A.tok_len, n_mx, nullptr, 1, totals)) || (rc = device_scan(c, A.hdr_len, A.hdr_len, n_seq, nullptr, 1, totals + 1))))
+        return pending_abort(c, p, rc);
+    if (e == hipSuccess) e = hipEventRecord(p.done, c->stream);
+    if (e == hipSuccess) e = p.wait(); /* the one wait */
+    if (e != hipSuccess) return pending_abort(c, p, fail(c, NTL_EDEVICE, std::string("ntl_sketch_format: ") + hipGetErrorString(e)));
+    const uint32_t *got = (const uint32_t *)p.slot;
+    t->bytes = (uint64_t)got[0] + got[1];
+    p.settle(c->pq);
+    if (t->bytes > bound) return fail(c, NTL_EINTERNAL, "ntl_sketch_format: the lengths exceed their bound");
+    if ((rc = t->text.alloc(c, t->bytes + 16))) return rc;
+    A.text = t->text.as<char>();
+    hipLaunchKernelGGL((sktext_kernel<true>), dim3(grid), dim3(SKTEXT_NT), 0, c->stream, A);
+    HIPCHK(c, hipGetLastError());
+    *out = t.release();
+    return NTL_OK;
+}
+
+extern "C" uint64_t ntl_sktext_bytes(const ntl_sktext *t) { return t ? t->bytes : 0; }
+
+extern "C" int ntl_sktext_download(const ntl_sktext *t, char *out)
+{
+    if (!t || (t->bytes && !out)) return NTL_EINVAL;
+    ntl_ctx *c = t->c;
+    (void)hipSetDevice(c->device);
+    if (!t->bytes) return NTL_OK;
+    HIPCHK(c, hipMemcpyAsync(out, t->text.p, t->bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, main_wait(c));
+    return NTL_OK;
+}
+
+extern "C" void ntl_sktext_destroy(ntl_sktext *t)
 {
     if (!t) return;
     (void)hipSetDevice(t->c->device);

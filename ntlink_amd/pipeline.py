@@ -147,12 +147,37 @@ def finish_pairs(tally, prefix, n, a, write_pairs_tsv):
     return len(pairs)
 
 
-def run_indexlr(dev, paths, k, w, out, with_len, batch_bases=DEFAULT_BATCH_BASES, with_strand=True):
+def device_text_on(device_text=None):
+    """The switch of the sketch text made on the device (capi.Sketch.text): None reads NTL_INDEXLR_DEVICE_TEXT, whose default is 0."""
+    return os.environ.get("NTL_INDEXLR_DEVICE_TEXT", "0") == "1" if device_text is None else bool(device_text)
+
+
+def write_sketch_text(dev, out, sk, names, lengths, with_len, with_strand, put):
+    """<id>\\t[len\\t]H:pos[:strand] ... of a resident sketch, formatted on the device: every piece goes to put(piece) in order --
+    `write_text_piece(dev, out, piece)` on a drain thread, or called directly.  No record array is downloaded."""
+    with dev.names(names, lengths) as tab:
+        for piece in sk.text(tab, with_len, with_strand):
+            put(piece)
+
+
+def write_text_piece(dev, out, piece):
+    try:
+        formats.write_blob(out, piece)
+    finally:
+        dev.pinned_release(piece)
+
+
+def run_indexlr(dev, paths, k, w, out, with_len, batch_bases=DEFAULT_BATCH_BASES, with_strand=True, device_text=None):
     """Sketch FASTA/FASTQ files on the device and print indexlr's TSV.  Three stages on threads: the reader
     parses the next batch into page-locked memory, the device sketches the current one, the emitter
-    formats and writes the previous one."""
+    formats and writes the previous one.  device_text (None: NTL_INDEXLR_DEVICE_TEXT=1; the default is off): the device formats
+    too (ntl_sketch_format) and the emitter only writes the pieces -- the same bytes."""
+    device_text = device_text_on(device_text)
     batches = Prefetch(seqio.load(paths, max_bases=batch_bases, alloc=dev.pinned_empty))
-    drain = Drain(lambda names, lens, off, h, p, s: formats.write_indexlr(out, names, lens, off, h, p, s, with_len, with_strand))
+    if device_text:
+        drain = Drain(lambda piece: write_text_piece(dev, out, piece))
+    else:
+        drain = Drain(lambda names, lens, off, h, p, s: formats.write_indexlr(out, names, lens, off, h, p, s, with_len, with_strand))
     try:
         for ss in batches:
             if not len(ss):
@@ -161,6 +186,9 @@ def run_indexlr(dev, paths, k, w, out, with_len, batch_bases=DEFAULT_BATCH_BASES
                 dev.pinned_release(ss.buf)
                 ss.buf = None
                 with dev.sketch(b, k, w) as sk:
+                    if device_text:
+                        write_sketch_text(dev, out, sk, ss.names, ss.lengths, with_len, with_strand, drain.put)
+                        continue
                     off, h, p, s = sk.download()
             drain.put(ss.names, ss.lengths, off, h, p, s)
         drain.close()
@@ -663,8 +691,11 @@ def _map_batches(dev, ix, batches, drain, stats, t_mark, w, first=None, text=Non
 
 def run_pair(dev, target, reads, prefix=None, k=32, w=100, n=1, a=1, z=1000, f=10, x=0.0, paf=False, verbose=True,
              sensitive=False, repeats=False, pairs_tsv=False, batch_bases=DEFAULT_BATCH_BASES, write_contig_tsv=True,
-             comm=None, device_tally=None):
+             comm=None, device_tally=None, device_text=None):
     """`ntLink pair target=T reads='R1 R2' k= w= ...`: the fused device path.
+
+    device_text (None: NTL_INDEXLR_DEVICE_TEXT=1 turns it on; the default is off): the lines of <target>.k<k>.w<w>.tsv are made on the
+    device (capi.Sketch.text) instead of from the downloaded records; the same bytes.
 
     device_tally (None: NTL_DEVICE_TALLY=1 turns it on; the default is off): every batch's pair records are made on the device
     (capi.Device.mapres_pairs) and the host keeps the dictionary only; with verbose=False paf=False no text is made and no mapping or
@@ -730,8 +761,15 @@ def run_pair(dev, target, reads, prefix=None, k=32, w=100, n=1, a=1, z=1000, f=1
         with open(f"{target}.k{k}.w{w}.tsv", "w") as fh:
             formats.write_indexlr(fh, ctg.names, ctg_len, off, h, p, s, False)
 
+    # NTL_INDEXLR_DEVICE_TEXT=1 (device_text): the contig TSV's lines are made on the device too; the drain thread writes the pieces
+    contig_text = device_text_on(device_text)
+    tsv_fh = []
+
+    def emit_contig_piece(piece):
+        write_text_piece(dev, tsv_fh[0], piece)
+
     drain = Drain(consume)  # text emitters + pair tally run behind the device
-    tsv_drain = Drain(emit_contig_tsv) if root and write_contig_tsv else None
+    tsv_drain = Drain(emit_contig_piece if contig_text else emit_contig_tsv) if root and write_contig_tsv else None
     stats = dict(read_bases=0, reads=0, read_minimizers=0, index_hits=0, t_contigs=0.0, t_ingest=0.0, t_device=0.0, t_handover=0.0, t_device_parts={})
     try:
         with (dev.batch_packed(ctg) if ctg.packed is not None else dev.batch(ctg.buf, ctg.offsets)) as cb:
@@ -757,7 +795,11 @@ def run_pair(dev, target, reads, prefix=None, k=32, w=100, n=1, a=1, z=1000, f=1
                         # <target>.k<k>.w<w>.tsv: its records come off the device while the other workers already map reads,
                         # and are written while the reads are mapped
                         t0 = time.perf_counter()
-                        tsv_drain.put(*csk.download())
+                        if contig_text:
+                            tsv_fh.append(open(f"{target}.k{k}.w{w}.tsv", "w"))
+                            write_sketch_text(dev, tsv_fh[0], csk, ctg.names, ctg_len, False, True, tsv_drain.put)
+                        else:
+                            tsv_drain.put(*csk.download())
                         stats["t_contigs_parts"]["download_for_tsv_beside_mapping"] = round(time.perf_counter() - t0, 4)
                     # NTL_DEVICE_TEXT=0: records cross PCIe and the host's emitter threads format them (ntl_write_verbose / _paf)
                     ctg_tab = dev.names(ctg.names, ctg_len) if os.environ.get("NTL_DEVICE_TEXT", "1") != "0" else None
@@ -776,6 +818,8 @@ def run_pair(dev, target, reads, prefix=None, k=32, w=100, n=1, a=1, z=1000, f=1
         drain.close()
         if tsv_drain:
             tsv_drain.close()
+        for fh in tsv_fh:
+            fh.close()
         out.close()
         stats["t_drain_tail"] = time.perf_counter() - t_fin  # writers still busy after the last device batch
         stats["parsed_bytes"] = io_stats.get("parsed_bytes", 0)
@@ -824,6 +868,11 @@ def run_pair(dev, target, reads, prefix=None, k=32, w=100, n=1, a=1, z=1000, f=1
                     d.close()
             except BaseException:
                 pass
+        for fh in tsv_fh:  # a contig TSV that was still being assembled from pieces is not left half made
+            if not fh.closed:
+                fh.close()
+                if os.path.exists(fh.name):
+                    os.remove(fh.name)
         out.remove_partial()
         batches.stop()
         raise
